@@ -5,13 +5,27 @@ Measures whole-job images/sec at 224^2, bf16, synthetic data, random-init
 weights, full train step (forward + loss + backward + DDP gradient all-reduce
 + SGD update) on N GPUs of one node.
 
-BASELINE.json's headline metric names BOTH ResNet-50 and ViT-B/16: the default
-invocation (no --model flag) measures both back-to-back and emits ONE JSON
-line whose value is the ResNet-50 images/s, with the ViT-B/16 number carried
-in config.models. Pass --model to measure a single model.
+The headline value is the ResNet-50 images/s. A plain run (no --model, no
+--full) measures only that: set up, warm up, time --steps steps, print ONE
+JSON line. BASELINE.json's headline metric names BOTH ResNet-50 and ViT-B/16:
+--full measures both back-to-back and carries the ViT-B/16 number in
+config.models of the same line. Pass --model to measure a single model.
+
+--dump-outputs DIR writes what the last timed step hands its caller (the loss
+it returns and a seeded sample of the parameters it updated) as
+DIR/<model>.<name>.npy, float32, so two builds can be compared output for
+output on identical seeded inputs.
+
+--lr defaults to 0: same kernels and same time per step as at any lr, but
+the weights stay at their seeded init, so the same arguments give the same
+parameters bit for bit and, for ResNet-50, a loss equal to about 3e-4. With
+lr > 0 the ResNet-50 outputs of two runs drift apart in proportion to lr,
+because the random-init net amplifies the order of the fp32 atomic BN sums
+(figures and method: profiles/bench_repeatability.txt). --lr 0.1 gives the
+earlier training trajectory; ViT-B/16 repeats bit for bit at either value.
 
 Launch (driver contract):
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
 """
@@ -19,9 +33,12 @@ from __future__ import annotations
 
 import argparse
 import json
+import os
 import sys
 import time
+from pathlib import Path
 
+import numpy as np
 import torch
 
 from deeplearning_amd.core.dist import (barrier, cleanup, get_rank,
@@ -39,24 +56,58 @@ def parse_args():
     p.add_argument("--warmup", type=int, default=10)
     p.add_argument("--model", default="all",
                    choices=["all", "resnet50", "vit_b16"],
-                   help="'all' (default) = both headline models, "
-                        "value = ResNet-50 img/s, ViT in config.models")
+                   help="'all' (default) = the headline ResNet-50 img/s; "
+                        "with --full also ViT-B/16, in config.models")
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beyond the headline figure "
+                        "(the second headline model, ViT-B/16)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs to "
+                        "DIR/<model>.<name>.npy (float32)")
     p.add_argument("--batch-size", type=int, default=0,
                    help="per-GPU batch (0 = model default)")
     p.add_argument("--dp", default="bucketed", choices=["bucketed", "torch"])
     p.add_argument("--bucket-mb", type=float, default=64.0,
                    help="DDP gradient-bucket size sweep knob (16/32/64/128)")
     p.add_argument("--no-channels-last", action="store_true")
-    p.add_argument("--lr", type=float, default=0.1)
+    p.add_argument("--lr", type=float, default=0.0,
+                   help="SGD learning rate; 0 (default) keeps the outputs "
+                        "reproducible from run to run, timing is the same")
     p.add_argument("--graph", default="off", choices=["auto", "on", "off"],
                    help="capture the train step in a hipGraph (single-GPU "
                         "only; removes per-kernel launch overhead)")
     return p.parse_args()
 
 
+PARAM_SAMPLE = 1 << 20  # elements of the flat parameter vector that are dumped
+
+
+def dump_outputs(out_dir, model_name, loss, params):
+    """Write what the last timed step hands its caller as float32 .npy files:
+    the loss it returns, and a fixed seeded sample of the parameters it
+    updated (the full vector of a 25-86 M parameter model would be hundreds
+    of MB)."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    flat = torch.cat([p.detach().float().reshape(-1) for p in params])
+    n = flat.numel()
+    if n > PARAM_SAMPLE:
+        idx = np.sort(np.random.default_rng(2024).choice(
+            n, size=PARAM_SAMPLE, replace=False))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    arrays = {
+        "loss": loss.detach().float().reshape(1),
+        "params_sample": flat,
+    }
+    for name, t in arrays.items():
+        np.save(out / f"{model_name}.{name}.npy",
+                t.cpu().numpy().astype(np.float32, copy=False))
+
+
 def run_model(args, model_name, device, world, rank, has_gpu):
     """Time one model's train loop; returns (images_per_sec, ms_per_step,
     global_batch) with elapsed maxed over ranks."""
+    t_start = time.perf_counter()
     per_gpu_batch = args.batch_size
     if per_gpu_batch == 0:
         per_gpu_batch = 256 if has_gpu else 8
@@ -103,6 +154,7 @@ def run_model(args, model_name, device, world, rank, has_gpu):
         one_step(i, set_to_none=not use_graph)
 
     graph = None
+    last = None  # loss of the most recent timed step
     if use_graph:
         # capture one full train step (fwd + loss + bwd + SGD) as a hipGraph;
         # replay re-executes every kernel on the same static batch buffers
@@ -115,11 +167,11 @@ def run_model(args, model_name, device, world, rank, has_gpu):
             torch.cuda.current_stream().wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                one_step(0, set_to_none=False)
+                last = one_step(0, set_to_none=False)
         except Exception as e:  # capture unsupported for this model: run eager
             print(f"[bench] graph capture failed ({e}); eager path",
                   file=sys.stderr)
-            graph = None
+            graph = last = None
 
     barrier()
     if has_gpu:
@@ -135,7 +187,7 @@ def run_model(args, model_name, device, world, rank, has_gpu):
                 static_y.copy_(src_y)
             graph.replay()
         else:
-            one_step(args.warmup + i)
+            last = one_step(args.warmup + i)
     barrier()
     if has_gpu:
         torch.cuda.synchronize()
@@ -149,8 +201,15 @@ def run_model(args, model_name, device, world, rank, has_gpu):
 
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed_max = float(t.item())
+    print(f"[bench] {model_name}: setup+warmup {t0 - t_start:.1f} s, "
+          f"{args.steps} timed steps {elapsed:.3f} s",
+          file=sys.stderr, flush=True)
 
-    del graph, model, optimizer, loader, batches, static_x, static_y
+    if args.dump_outputs and rank == 0 and last is not None:
+        dump_outputs(args.dump_outputs, model_name, last, params)
+
+    del last, params, graph, model, optimizer, loader, batches
+    del static_x, static_y
     if has_gpu:
         torch.cuda.empty_cache()
 
@@ -170,13 +229,25 @@ def main():
     if has_gpu:
         torch.cuda.set_device(device)
         torch.backends.cudnn.benchmark = True
+        # cudnn.benchmark makes every process time all applicable MIOpen
+        # solvers per conv shape. The naive reference solvers take 30-300 ms
+        # a run (the chosen ones ~0.1 ms) and never win, yet timing them was
+        # most of every start-up (profiles/bench_startup.txt). Benchmark-only.
+        for d in ("FWD", "BWD", "WRW"):
+            os.environ.setdefault(f"MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_{d}",
+                                  "0")
     # rank-count evidence for the driver's SCALE record: every rank reports in
     print(f"[bench] rank {rank}/{world} local_rank {info['local_rank']} "
           f"device {device} backend "
           f"{'nccl(RCCL)' if has_gpu and world > 1 else ('gloo' if world > 1 else 'none')}",
           file=sys.stderr, flush=True)
 
-    model_names = ["vit_b16", "resnet50"] if args.model == "all" else [args.model]
+    if args.model != "all":
+        model_names = [args.model]
+    elif args.full:
+        model_names = ["vit_b16", "resnet50"]
+    else:
+        model_names = ["resnet50"]
     results = {}
     for name in model_names:
         img_s, ms, global_batch = run_model(args, name, device, world, rank,
