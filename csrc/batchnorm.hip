@@ -34,18 +34,14 @@ __global__ void bn_stats_kernel(const dev_t* __restrict__ x, float* __restrict__
 }
 
 // ---- finalize: mean/rstd + running-stat update + scale/shift ---------------
-__global__ void bn_finalize_kernel(const float* __restrict__ sums,
-                                   const float* __restrict__ weight,
-                                   const float* __restrict__ bias,
-                                   float* __restrict__ mean, float* __restrict__ rstd,
-                                   float* __restrict__ running_mean,
-                                   float* __restrict__ running_var,
-                                   float* __restrict__ scale, float* __restrict__ shift,
-                                   int C, float count, float eps, float momentum) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  const float mu = sums[c] / count;
-  const float var = fmaxf(sums[C + c] / count - mu * mu, 0.f);
+__device__ __forceinline__ void bn_finalize_channel(
+    int c, float sum, float sumsq, const float* __restrict__ weight,
+    const float* __restrict__ bias, float* __restrict__ mean,
+    float* __restrict__ rstd, float* __restrict__ running_mean,
+    float* __restrict__ running_var, float* __restrict__ scale,
+    float* __restrict__ shift, float count, float eps, float momentum) {
+  const float mu = sum / count;
+  const float var = fmaxf(sumsq / count - mu * mu, 0.f);
   const float rs = rsqrtf(var + eps);
   mean[c] = mu;
   rstd[c] = rs;
@@ -57,6 +53,64 @@ __global__ void bn_finalize_kernel(const float* __restrict__ sums,
   const float sc = weight[c] * rs;
   scale[c] = sc;
   shift[c] = bias[c] - mu * sc;
+}
+
+__global__ void bn_finalize_kernel(const float* __restrict__ sums,
+                                   const float* __restrict__ weight,
+                                   const float* __restrict__ bias,
+                                   float* __restrict__ mean, float* __restrict__ rstd,
+                                   float* __restrict__ running_mean,
+                                   float* __restrict__ running_var,
+                                   float* __restrict__ scale, float* __restrict__ shift,
+                                   int C, float count, float eps, float momentum) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  bn_finalize_channel(c, sums[c], sums[C + c], weight, bias, mean, rstd,
+                      running_mean, running_var, scale, shift, count, eps,
+                      momentum);
+}
+
+// Finalize straight from the conv epilogue's [n_parts, 2C] per-block partial
+// slab: each block owns kFinCh channels and sums the slab rows with kFinRows
+// row lanes (fixed-order LDS tree, so the result is deterministic), then one
+// lane per channel finalizes. Replaces a separate reduce launch per conv.
+constexpr int kFinCh = 16, kFinRows = 64;
+
+__global__ void __launch_bounds__(kFinCh * kFinRows)
+bn_finalize_parts_kernel(const float* __restrict__ parts, int n_parts,
+                         const float* __restrict__ weight,
+                         const float* __restrict__ bias,
+                         float* __restrict__ mean, float* __restrict__ rstd,
+                         float* __restrict__ running_mean,
+                         float* __restrict__ running_var,
+                         float* __restrict__ scale, float* __restrict__ shift,
+                         int C, float count, float eps, float momentum) {
+  __shared__ float ls[2][kFinRows][kFinCh + 1];
+  const int cl = threadIdx.x % kFinCh, rl = threadIdx.x / kFinCh;
+  const int c = blockIdx.x * kFinCh + cl;
+  float s = 0.f, q = 0.f;
+  if (c < C) {
+#pragma unroll 4
+    for (int r = rl; r < n_parts; r += kFinRows) {
+      const float* p = parts + (int64_t)r * 2 * C;
+      s += p[c];
+      q += p[C + c];
+    }
+  }
+  ls[0][rl][cl] = s;
+  ls[1][rl][cl] = q;
+  __syncthreads();
+  for (int h = kFinRows / 2; h > 0; h >>= 1) {
+    if (rl < h) {
+      ls[0][rl][cl] += ls[0][rl + h][cl];
+      ls[1][rl][cl] += ls[1][rl + h][cl];
+    }
+    __syncthreads();
+  }
+  if (rl == 0 && c < C)
+    bn_finalize_channel(c, ls[0][0][cl], ls[1][0][cl], weight, bias, mean,
+                        rstd, running_mean, running_var, scale, shift, count,
+                        eps, momentum);
 }
 
 // ---- pass 2 (also frozen-BN apply): y = x*scale[c] + shift[c] (+ReLU) ------
@@ -312,9 +366,222 @@ __global__ void bn_bwd_dx_nhwc_kernel(const dev_t* __restrict__ dy,
   }
 }
 
+// ---- fused residual join: out = relu(bn(x) + identity) ----------------------
+// DUAL: the identity is itself a raw conv output with its own BN (first block
+// of a stage): out = relu(x*sc + sh + xd*scd + shd). fp32 arithmetic, one
+// rounding to the output type; the BN output is never materialised.
+template <typename dev_t, int V, bool DUAL>
+__global__ void bn_add_relu_nhwc_kernel(const dev_t* __restrict__ x,
+                                        const float* __restrict__ scale,
+                                        const float* __restrict__ shift,
+                                        const dev_t* __restrict__ idn,
+                                        const float* __restrict__ scale_d,
+                                        const float* __restrict__ shift_d,
+                                        dev_t* __restrict__ out, int C,
+                                        int64_t rows, int64_t used) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= used) return;
+  const int lanes_per_row = C / V;
+  const int c0 = (int)(t % lanes_per_row) * V;
+  const int64_t rstride = used / lanes_per_row;
+  float sc[V], sh[V], scd[V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) {
+    sc[j] = scale[c0 + j];
+    sh[j] = shift[c0 + j];
+    if (DUAL) {
+      scd[j] = scale_d[c0 + j];
+      sh[j] += shift_d[c0 + j];
+    }
+  }
+  for (int64_t r = t / lanes_per_row; r < rows; r += rstride) {
+    const int64_t base = r * C + c0;
+    Vec<dev_t, V> xv = vload<dev_t, V>(x + base);
+    Vec<dev_t, V> iv = vload<dev_t, V>(idn + base);
+    Vec<dev_t, V> ov;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      float f = to_f32(xv.v[j]) * sc[j] + sh[j];
+      f += DUAL ? to_f32(iv.v[j]) * scd[j] : to_f32(iv.v[j]);
+      ov.v[j] = from_f32<dev_t>(fmaxf(f, 0.f));
+    }
+    vstore<dev_t, V>(out + base, ov);
+  }
+}
+
+// Join backward pass 1: g = dy * [out > 0] is written once (it is the
+// identity gradient and the input of pass 2), and sum(g), sum(g*xhat)
+// (DUAL: also sum(g*xhat_d)) reduce per channel through LDS.
+// sums layout: {sum g [C], sum g*xhat [C], sum g*xhat_d [C] (DUAL)}.
+template <typename dev_t, int V, bool DUAL>
+__global__ void bn_join_bwd_stats_nhwc_kernel(
+    const dev_t* __restrict__ dy, const dev_t* __restrict__ out,
+    const dev_t* __restrict__ x, const float* __restrict__ mean,
+    const float* __restrict__ rstd, const dev_t* __restrict__ xd,
+    const float* __restrict__ mean_d, const float* __restrict__ rstd_d,
+    dev_t* __restrict__ g_out, float* __restrict__ sums, int C, int64_t rows,
+    int64_t used) {
+  constexpr int NS = DUAL ? 3 : 2;
+  extern __shared__ float ls[];  // NS*C floats
+  for (int i = threadIdx.x; i < NS * C; i += blockDim.x) ls[i] = 0.f;
+  __syncthreads();
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int lanes_per_row = C / V;
+  if (t < used) {
+    const int c0 = (int)(t % lanes_per_row) * V;
+    const int64_t rstride = used / lanes_per_row;
+    float mu[V], rs[V], mud[V], rsd[V], s_g[V], s_gxh[V], s_gxhd[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      mu[j] = mean[c0 + j];
+      rs[j] = rstd[c0 + j];
+      mud[j] = DUAL ? mean_d[c0 + j] : 0.f;
+      rsd[j] = DUAL ? rstd_d[c0 + j] : 0.f;
+      s_g[j] = 0.f;
+      s_gxh[j] = 0.f;
+      s_gxhd[j] = 0.f;
+    }
+    for (int64_t r = t / lanes_per_row; r < rows; r += rstride) {
+      const int64_t base = r * C + c0;
+      Vec<dev_t, V> dyv = vload<dev_t, V>(dy + base);
+      Vec<dev_t, V> ov = vload<dev_t, V>(out + base);
+      Vec<dev_t, V> xv = vload<dev_t, V>(x + base);
+      Vec<dev_t, V> xdv;
+      if (DUAL) xdv = vload<dev_t, V>(xd + base);
+      Vec<dev_t, V> gv;
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        const bool on = to_f32(ov.v[j]) > 0.f;
+        gv.v[j] = on ? dyv.v[j] : from_f32<dev_t>(0.f);
+        const float g = on ? to_f32(dyv.v[j]) : 0.f;
+        s_g[j] += g;
+        s_gxh[j] += g * ((to_f32(xv.v[j]) - mu[j]) * rs[j]);
+        if (DUAL) s_gxhd[j] += g * ((to_f32(xdv.v[j]) - mud[j]) * rsd[j]);
+      }
+      vstore<dev_t, V>(g_out + base, gv);
+    }
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      atomicAdd(&ls[c0 + j], s_g[j]);
+      atomicAdd(&ls[C + c0 + j], s_gxh[j]);
+      if (DUAL) atomicAdd(&ls[2 * C + c0 + j], s_gxhd[j]);
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < NS * C; i += blockDim.x)
+    atomicAdd(&sums[i], ls[i]);
+}
+
+// Dual join backward pass 2: one read of g feeds both BNs' dx.
+// (The single join reuses bn_bwd_dx_nhwc_kernel<.., false> with dy = g.)
+template <typename dev_t, int V>
+__global__ void bn_join_bwd_dx_dual_nhwc_kernel(
+    const dev_t* __restrict__ g, const dev_t* __restrict__ x,
+    const dev_t* __restrict__ xd, const float* __restrict__ mean,
+    const float* __restrict__ rstd, const float* __restrict__ weight,
+    const float* __restrict__ mean_d, const float* __restrict__ rstd_d,
+    const float* __restrict__ weight_d, const float* __restrict__ sums,
+    dev_t* __restrict__ dx, dev_t* __restrict__ dxd, int C, int64_t rows,
+    int64_t used, float inv_count) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= used) return;
+  const int lanes_per_row = C / V;
+  const int c0 = (int)(t % lanes_per_row) * V;
+  const int64_t rstride = used / lanes_per_row;
+  float mu[V], rs[V], wr[V], mud[V], rsd[V], wrd[V], m_g[V], m_gxh[V],
+      m_gxhd[V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) {
+    mu[j] = mean[c0 + j];
+    rs[j] = rstd[c0 + j];
+    wr[j] = weight[c0 + j] * rs[j];
+    mud[j] = mean_d[c0 + j];
+    rsd[j] = rstd_d[c0 + j];
+    wrd[j] = weight_d[c0 + j] * rsd[j];
+    m_g[j] = sums[c0 + j] * inv_count;
+    m_gxh[j] = sums[C + c0 + j] * inv_count;
+    m_gxhd[j] = sums[2 * C + c0 + j] * inv_count;
+  }
+  for (int64_t r = t / lanes_per_row; r < rows; r += rstride) {
+    const int64_t base = r * C + c0;
+    Vec<dev_t, V> gv = vload<dev_t, V>(g + base);
+    Vec<dev_t, V> xv = vload<dev_t, V>(x + base);
+    Vec<dev_t, V> xdv = vload<dev_t, V>(xd + base);
+    Vec<dev_t, V> dxv, dxdv;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      const float gg = to_f32(gv.v[j]) - m_g[j];
+      const float xh = (to_f32(xv.v[j]) - mu[j]) * rs[j];
+      const float xhd = (to_f32(xdv.v[j]) - mud[j]) * rsd[j];
+      dxv.v[j] = from_f32<dev_t>(wr[j] * (gg - xh * m_gxh[j]));
+      dxdv.v[j] = from_f32<dev_t>(wrd[j] * (gg - xhd * m_gxhd[j]));
+    }
+    vstore<dev_t, V>(dx + base, dxv);
+    vstore<dev_t, V>(dxd + base, dxdv);
+  }
+}
+
 inline bool is_nhwc(const torch::Tensor& t) {
   return t.dim() == 4 && t.is_contiguous(at::MemoryFormat::ChannelsLast) &&
          !t.is_contiguous();
+}
+
+struct BnFinalized {
+  torch::Tensor mean, rstd, scale, shift;
+};
+
+// Launch the finalize step on `sums`: either the [2C] {sum, sumsq} vector or
+// the conv epilogue's [n_parts, 2C] partial slab (summed inside the kernel).
+inline BnFinalized bn_finalize_launch(
+    const torch::Tensor& sums, const torch::Tensor& weight,
+    const torch::Tensor& bias, c10::optional<torch::Tensor>& running_mean,
+    c10::optional<torch::Tensor>& running_var, int C, int64_t rows,
+    double momentum, double eps) {
+  TORCH_CHECK(sums.is_cuda() && sums.scalar_type() == torch::kFloat &&
+                  sums.is_contiguous(),
+              "bn sums must be a contiguous fp32 GPU tensor");
+  TORCH_CHECK((sums.dim() == 1 && sums.size(0) == 2 * C) ||
+                  (sums.dim() == 2 && sums.size(0) >= 1 &&
+                   sums.size(1) == 2 * C),
+              "bn sums must be [2C] or [n_parts, 2C]");
+  TORCH_CHECK(weight.numel() == C && bias.numel() == C,
+              "bn weight/bias must have C elements");
+  auto opts_f = sums.options();
+  BnFinalized f{torch::empty({C}, opts_f), torch::empty({C}, opts_f),
+                torch::empty({C}, opts_f), torch::empty({C}, opts_f)};
+  auto w32 = weight.to(torch::kFloat).contiguous();
+  auto b32 = bias.to(torch::kFloat).contiguous();
+  float* rm = running_mean.has_value() ? running_mean->data_ptr<float>() : nullptr;
+  float* rv = running_var.has_value() ? running_var->data_ptr<float>() : nullptr;
+  const int n_parts = sums.dim() == 2 ? (int)sums.size(0) : 1;
+  if (n_parts > 1) {
+    hipLaunchKernelGGL(bn_finalize_parts_kernel, dim3((C + kFinCh - 1) / kFinCh),
+                       dim3(kFinCh * kFinRows), 0, stream(),
+                       sums.data_ptr<float>(), n_parts, w32.data_ptr<float>(),
+                       b32.data_ptr<float>(), f.mean.data_ptr<float>(),
+                       f.rstd.data_ptr<float>(), rm, rv,
+                       f.scale.data_ptr<float>(), f.shift.data_ptr<float>(), C,
+                       (float)rows, (float)eps, (float)momentum);
+  } else {
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0,
+                       stream(), sums.data_ptr<float>(), w32.data_ptr<float>(),
+                       b32.data_ptr<float>(), f.mean.data_ptr<float>(),
+                       f.rstd.data_ptr<float>(), rm, rv,
+                       f.scale.data_ptr<float>(), f.shift.data_ptr<float>(), C,
+                       (float)rows, (float)eps, (float)momentum);
+  }
+  return f;
+}
+
+// dweight / dbias as views of the backward sums buffer: no device copy when
+// the parameter is fp32, one conversion otherwise.
+inline torch::Tensor bn_param_grad(const torch::Tensor& sums, int64_t offset,
+                                   int C, const torch::Tensor& weight) {
+  return sums.narrow(0, offset, C).to(weight.scalar_type());
+}
+
+inline bool is_nhwc_rows(const torch::Tensor& t) {
+  return t.dim() == 4 && t.is_contiguous(at::MemoryFormat::ChannelsLast);
 }
 
 }  // namespace dla
@@ -413,7 +680,8 @@ std::vector<torch::Tensor> batchnorm_fwd(torch::Tensor x, torch::Tensor weight,
 // Train-mode BN forward with the stats pass ALREADY DONE by the producing
 // kernel (conv1x1_fwd's fused sum/sumsq epilogue): finalize + apply only —
 // saves one full read pass over x vs batchnorm_fwd. sums layout matches
-// bn_stats: [2C] = {sum[c], sumsq[C+c]}.
+// bn_stats: [2C] = {sum[c], sumsq[C+c]}, or the conv epilogue's per-block
+// [n_parts, 2C] slab, which the finalize kernel sums itself.
 std::vector<torch::Tensor> batchnorm_fwd_from_sums(
     torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
     torch::Tensor sums, c10::optional<torch::Tensor> running_mean,
@@ -426,25 +694,15 @@ std::vector<torch::Tensor> batchnorm_fwd_from_sums(
               "batchnorm_fwd_from_sums: x must be contiguous");
   const int N = (int)x.size(0), C = (int)x.size(1);
   const int64_t HW = x.size(2) * x.size(3);
-  TORCH_CHECK(sums.numel() == 2 * C, "sums must be [2C]");
-  auto opts_f = x.options().dtype(torch::kFloat);
-  auto mean = torch::empty({C}, opts_f);
-  auto rstd = torch::empty({C}, opts_f);
-  auto scale = torch::empty({C}, opts_f);
-  auto shift = torch::empty({C}, opts_f);
   auto y = torch::empty_like(x);
-  auto w32 = weight.to(torch::kFloat);
-  auto b32 = bias.to(torch::kFloat);
   const int64_t rows = (int64_t)N * HW;
+  auto fin = dla::bn_finalize_launch(sums, weight, bias, running_mean,
+                                     running_var, C, rows, momentum, eps);
+  auto& mean = fin.mean;
+  auto& rstd = fin.rstd;
+  auto& scale = fin.scale;
+  auto& shift = fin.shift;
   DLA_DISPATCH_FLOAT_TYPES(x.scalar_type(), "batchnorm_fwd_from_sums", [&] {
-    hipLaunchKernelGGL(dla::bn_finalize_kernel, dim3((C + 255) / 256), dim3(256),
-                       0, dla::stream(), sums.data_ptr<float>(),
-                       w32.data_ptr<float>(), b32.data_ptr<float>(),
-                       mean.data_ptr<float>(), rstd.data_ptr<float>(),
-                       running_mean.has_value() ? running_mean->data_ptr<float>() : nullptr,
-                       running_var.has_value() ? running_var->data_ptr<float>() : nullptr,
-                       scale.data_ptr<float>(), shift.data_ptr<float>(), C,
-                       (float)rows, (float)eps, (float)momentum);
     const int64_t n_total = x.numel();
     constexpr int VMAX = 16 / (int)sizeof(dev_t);
     auto launch = [&](auto vtag, auto rtag) {
@@ -616,7 +874,197 @@ std::vector<torch::Tensor> batchnorm_bwd(torch::Tensor dy, torch::Tensor x,
     }
   });
   HIP_CHECK_ERR();
-  auto dweight = sums.narrow(0, C, C).clone().to(weight.scalar_type());
-  auto dbias = sums.narrow(0, 0, C).clone().to(weight.scalar_type());
-  return {dx, dweight, dbias};
+  return {dx, dla::bn_param_grad(sums, C, C, weight),
+          dla::bn_param_grad(sums, 0, C, weight)};
+}
+
+// ---- fused residual join ----------------------------------------------------
+namespace dla {
+
+inline void join_check(const torch::Tensor& x, const torch::Tensor& other,
+                       const char* what) {
+  TORCH_CHECK(other.is_cuda() && other.scalar_type() == x.scalar_type() &&
+                  other.sizes() == x.sizes() && is_nhwc_rows(other),
+              "bn join: ", what, " must match x (shape, dtype, channels_last)");
+}
+
+inline int join_vec(const torch::Tensor& x) {
+  const int vmax = 16 / (int)x.element_size();
+  TORCH_CHECK(x.size(1) % vmax == 0,
+              "bn join: C must be a multiple of ", vmax);
+  return vmax;
+}
+
+}  // namespace dla
+
+// out = relu(bn(x) + identity), BN finalized from the conv-fused sums
+// ([2C] or [n_parts, 2C]). Returns {out, save_mean, save_rstd}.
+std::vector<torch::Tensor> bn_add_relu_fwd_from_sums(
+    torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
+    torch::Tensor sums, c10::optional<torch::Tensor> running_mean,
+    c10::optional<torch::Tensor> running_var, double momentum, double eps,
+    torch::Tensor identity) {
+  DLA_CHECK_CUDA(x);
+  TORCH_CHECK(dla::is_nhwc_rows(x), "bn_add_relu: x must be channels_last");
+  dla::join_check(x, identity, "identity");
+  dla::join_vec(x);
+  const int C = (int)x.size(1);
+  const int64_t rows = x.numel() / C;
+  auto fin = dla::bn_finalize_launch(sums, weight, bias, running_mean,
+                                     running_var, C, rows, momentum, eps);
+  auto out = torch::empty_like(x);
+  DLA_DISPATCH_FLOAT_TYPES(x.scalar_type(), "bn_add_relu_fwd_from_sums", [&] {
+    constexpr int V = 16 / (int)sizeof(dev_t);
+    const int64_t used = dla::nhwc_used_threads(C / V, rows, 524288);
+    hipLaunchKernelGGL((dla::bn_add_relu_nhwc_kernel<dev_t, V, false>),
+                       dim3((int)((used + 255) / 256)), dim3(256), 0,
+                       dla::stream(), (const dev_t*)x.data_ptr(),
+                       fin.scale.data_ptr<float>(), fin.shift.data_ptr<float>(),
+                       (const dev_t*)identity.data_ptr(), nullptr, nullptr,
+                       (dev_t*)out.data_ptr(), C, rows, used);
+  });
+  HIP_CHECK_ERR();
+  return {out, fin.mean, fin.rstd};
+}
+
+// out = relu(bn(x) + bn_d(xd)): both operands are raw conv outputs.
+// Returns {out, mean, rstd, mean_d, rstd_d}.
+std::vector<torch::Tensor> bn_add_relu_dual_fwd_from_sums(
+    torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
+    torch::Tensor sums, c10::optional<torch::Tensor> running_mean,
+    c10::optional<torch::Tensor> running_var, double momentum, double eps,
+    torch::Tensor xd, torch::Tensor weight_d, torch::Tensor bias_d,
+    torch::Tensor sums_d, c10::optional<torch::Tensor> running_mean_d,
+    c10::optional<torch::Tensor> running_var_d, double momentum_d,
+    double eps_d) {
+  DLA_CHECK_CUDA(x);
+  TORCH_CHECK(dla::is_nhwc_rows(x), "bn_add_relu_dual: x must be channels_last");
+  dla::join_check(x, xd, "xd");
+  dla::join_vec(x);
+  const int C = (int)x.size(1);
+  const int64_t rows = x.numel() / C;
+  auto fin = dla::bn_finalize_launch(sums, weight, bias, running_mean,
+                                     running_var, C, rows, momentum, eps);
+  auto fd = dla::bn_finalize_launch(sums_d, weight_d, bias_d, running_mean_d,
+                                    running_var_d, C, rows, momentum_d, eps_d);
+  auto out = torch::empty_like(x);
+  DLA_DISPATCH_FLOAT_TYPES(x.scalar_type(), "bn_add_relu_dual_fwd_from_sums", [&] {
+    constexpr int V = 16 / (int)sizeof(dev_t);
+    const int64_t used = dla::nhwc_used_threads(C / V, rows, 524288);
+    hipLaunchKernelGGL((dla::bn_add_relu_nhwc_kernel<dev_t, V, true>),
+                       dim3((int)((used + 255) / 256)), dim3(256), 0,
+                       dla::stream(), (const dev_t*)x.data_ptr(),
+                       fin.scale.data_ptr<float>(), fin.shift.data_ptr<float>(),
+                       (const dev_t*)xd.data_ptr(), fd.scale.data_ptr<float>(),
+                       fd.shift.data_ptr<float>(), (dev_t*)out.data_ptr(), C,
+                       rows, used);
+  });
+  HIP_CHECK_ERR();
+  return {out, fin.mean, fin.rstd, fd.mean, fd.rstd};
+}
+
+// Backward of the single join. Returns {g, dx, dweight, dbias}; g = dy*[out>0]
+// is the identity gradient itself (not a copy).
+std::vector<torch::Tensor> bn_add_relu_bwd(torch::Tensor dy, torch::Tensor out,
+                                           torch::Tensor x, torch::Tensor weight,
+                                           torch::Tensor mean,
+                                           torch::Tensor rstd) {
+  DLA_CHECK_CUDA(x);
+  TORCH_CHECK(dla::is_nhwc_rows(x), "bn_add_relu_bwd: x must be channels_last");
+  dla::join_check(x, out, "out");
+  if (!dla::is_nhwc_rows(dy)) dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
+  dla::join_check(x, dy, "dy");
+  dla::join_vec(x);
+  const int C = (int)x.size(1);
+  const int64_t rows = x.numel() / C;
+  TORCH_CHECK(mean.numel() == C && rstd.numel() == C && weight.numel() == C,
+              "bn_add_relu_bwd: per-channel tensors must have C elements");
+  auto sums = torch::zeros({2 * C}, x.options().dtype(torch::kFloat));
+  auto g = torch::empty_like(x);
+  auto dx = torch::empty_like(x);
+  auto w32 = weight.to(torch::kFloat).contiguous();
+  DLA_DISPATCH_FLOAT_TYPES(x.scalar_type(), "bn_add_relu_bwd", [&] {
+    constexpr int V = 16 / (int)sizeof(dev_t);
+    const int lanes = C / V;
+    const int64_t used_s = dla::nhwc_used_threads(lanes, rows, 262144);
+    hipLaunchKernelGGL((dla::bn_join_bwd_stats_nhwc_kernel<dev_t, V, false>),
+                       dim3((int)((used_s + 255) / 256)), dim3(256),
+                       2 * C * sizeof(float), dla::stream(),
+                       (const dev_t*)dy.data_ptr(), (const dev_t*)out.data_ptr(),
+                       (const dev_t*)x.data_ptr(), mean.data_ptr<float>(),
+                       rstd.data_ptr<float>(), nullptr, nullptr, nullptr,
+                       (dev_t*)g.data_ptr(), sums.data_ptr<float>(), C, rows,
+                       used_s);
+    const int64_t used = dla::nhwc_used_threads(lanes, rows, 524288);
+    hipLaunchKernelGGL((dla::bn_bwd_dx_nhwc_kernel<dev_t, V, false>),
+                       dim3((int)((used + 255) / 256)), dim3(256), 0,
+                       dla::stream(), (const dev_t*)g.data_ptr(),
+                       (const dev_t*)x.data_ptr(), nullptr,
+                       mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                       w32.data_ptr<float>(), sums.data_ptr<float>(),
+                       (dev_t*)dx.data_ptr(), C, rows, used,
+                       1.f / (float)rows);
+  });
+  HIP_CHECK_ERR();
+  return {g, dx, dla::bn_param_grad(sums, C, C, weight),
+          dla::bn_param_grad(sums, 0, C, weight)};
+}
+
+// Backward of the dual join. Returns {dx, dxd, dweight, dbias, dweight_d,
+// dbias_d}; sum g is shared, so dbias_d holds the same values as dbias.
+std::vector<torch::Tensor> bn_add_relu_dual_bwd(
+    torch::Tensor dy, torch::Tensor out, torch::Tensor x, torch::Tensor weight,
+    torch::Tensor mean, torch::Tensor rstd, torch::Tensor xd,
+    torch::Tensor weight_d, torch::Tensor mean_d, torch::Tensor rstd_d) {
+  DLA_CHECK_CUDA(x);
+  TORCH_CHECK(dla::is_nhwc_rows(x), "bn_add_relu_dual_bwd: x must be channels_last");
+  dla::join_check(x, out, "out");
+  dla::join_check(x, xd, "xd");
+  if (!dla::is_nhwc_rows(dy)) dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
+  dla::join_check(x, dy, "dy");
+  dla::join_vec(x);
+  const int C = (int)x.size(1);
+  const int64_t rows = x.numel() / C;
+  TORCH_CHECK(mean.numel() == C && rstd.numel() == C && weight.numel() == C &&
+                  mean_d.numel() == C && rstd_d.numel() == C &&
+                  weight_d.numel() == C,
+              "bn_add_relu_dual_bwd: per-channel tensors must have C elements");
+  auto sums = torch::zeros({3 * C}, x.options().dtype(torch::kFloat));
+  auto g = torch::empty_like(x);
+  auto dx = torch::empty_like(x);
+  auto dxd = torch::empty_like(x);
+  auto w32 = weight.to(torch::kFloat).contiguous();
+  auto wd32 = weight_d.to(torch::kFloat).contiguous();
+  DLA_DISPATCH_FLOAT_TYPES(x.scalar_type(), "bn_add_relu_dual_bwd", [&] {
+    constexpr int V = 16 / (int)sizeof(dev_t);
+    const int lanes = C / V;
+    const int64_t used_s = dla::nhwc_used_threads(lanes, rows, 262144);
+    hipLaunchKernelGGL((dla::bn_join_bwd_stats_nhwc_kernel<dev_t, V, true>),
+                       dim3((int)((used_s + 255) / 256)), dim3(256),
+                       3 * C * sizeof(float), dla::stream(),
+                       (const dev_t*)dy.data_ptr(), (const dev_t*)out.data_ptr(),
+                       (const dev_t*)x.data_ptr(), mean.data_ptr<float>(),
+                       rstd.data_ptr<float>(), (const dev_t*)xd.data_ptr(),
+                       mean_d.data_ptr<float>(), rstd_d.data_ptr<float>(),
+                       (dev_t*)g.data_ptr(), sums.data_ptr<float>(), C, rows,
+                       used_s);
+    const int64_t used = dla::nhwc_used_threads(lanes, rows, 524288);
+    hipLaunchKernelGGL((dla::bn_join_bwd_dx_dual_nhwc_kernel<dev_t, V>),
+                       dim3((int)((used + 255) / 256)), dim3(256), 0,
+                       dla::stream(), (const dev_t*)g.data_ptr(),
+                       (const dev_t*)x.data_ptr(), (const dev_t*)xd.data_ptr(),
+                       mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                       w32.data_ptr<float>(), mean_d.data_ptr<float>(),
+                       rstd_d.data_ptr<float>(), wd32.data_ptr<float>(),
+                       sums.data_ptr<float>(), (dev_t*)dx.data_ptr(),
+                       (dev_t*)dxd.data_ptr(), C, rows, used,
+                       1.f / (float)rows);
+  });
+  HIP_CHECK_ERR();
+  // sum g serves both biases, but two parameters must not share gradient
+  // storage (optimizers update .grad in place): the second gets a copy
+  auto dbias = dla::bn_param_grad(sums, 0, C, weight);
+  return {dx, dxd, dla::bn_param_grad(sums, C, C, weight), dbias,
+          dla::bn_param_grad(sums, 2 * C, C, weight_d),
+          dbias.to(weight_d.scalar_type()).clone()};
 }

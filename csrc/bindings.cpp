@@ -31,6 +31,27 @@ std::vector<torch::Tensor> batchnorm_fwd_from_sums(
     torch::Tensor sums, c10::optional<torch::Tensor> running_mean,
     c10::optional<torch::Tensor> running_var, double momentum, double eps,
     bool relu);
+std::vector<torch::Tensor> bn_add_relu_fwd_from_sums(
+    torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
+    torch::Tensor sums, c10::optional<torch::Tensor> running_mean,
+    c10::optional<torch::Tensor> running_var, double momentum, double eps,
+    torch::Tensor identity);
+std::vector<torch::Tensor> bn_add_relu_dual_fwd_from_sums(
+    torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
+    torch::Tensor sums, c10::optional<torch::Tensor> running_mean,
+    c10::optional<torch::Tensor> running_var, double momentum, double eps,
+    torch::Tensor xd, torch::Tensor weight_d, torch::Tensor bias_d,
+    torch::Tensor sums_d, c10::optional<torch::Tensor> running_mean_d,
+    c10::optional<torch::Tensor> running_var_d, double momentum_d,
+    double eps_d);
+std::vector<torch::Tensor> bn_add_relu_bwd(torch::Tensor dy, torch::Tensor out,
+                                           torch::Tensor x, torch::Tensor weight,
+                                           torch::Tensor mean,
+                                           torch::Tensor rstd);
+std::vector<torch::Tensor> bn_add_relu_dual_bwd(
+    torch::Tensor dy, torch::Tensor out, torch::Tensor x, torch::Tensor weight,
+    torch::Tensor mean, torch::Tensor rstd, torch::Tensor xd,
+    torch::Tensor weight_d, torch::Tensor mean_d, torch::Tensor rstd_d);
 // conv1x1.hip
 std::vector<torch::Tensor> conv1x1_fwd(torch::Tensor a, torch::Tensor b,
                                        c10::optional<torch::Tensor> bias,
@@ -121,6 +142,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("batchnorm_fwd_from_sums", &batchnorm_fwd_from_sums);
   m.def("bn_apply", &bn_apply);
   m.def("batchnorm_bwd", &batchnorm_bwd);
+  m.def("bn_add_relu_fwd_from_sums", &bn_add_relu_fwd_from_sums);
+  m.def("bn_add_relu_dual_fwd_from_sums", &bn_add_relu_dual_fwd_from_sums);
+  m.def("bn_add_relu_bwd", &bn_add_relu_bwd);
+  m.def("bn_add_relu_dual_bwd", &bn_add_relu_dual_bwd);
   m.def("conv1x1_fwd", &conv1x1_fwd, py::arg("a"), py::arg("b"),
         py::arg("bias") = py::none(), py::arg("scale") = py::none(),
         py::arg("shift") = py::none(), py::arg("residual") = py::none(),

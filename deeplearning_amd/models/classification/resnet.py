@@ -7,7 +7,9 @@ every 1x1 conv (bottleneck conv1/conv3, downsample) runs the hand-written
 implicit-GEMM MFMA kernel with the BatchNorm stats pass fused into the conv
 epilogue (csrc/conv1x1.hip); 3x3 convs run MIOpen by default with a fully
 hand-written TAPS=9 route available (DLA_CONV3X3=1, see ROADMAP); each
-residual join is one fused add+relu kernel.
+Bottleneck join is one kernel that applies bn3 (and the downsample bn), adds
+the identity and applies ReLU (DLA_NO_FUSED_JOIN=1 restores bn apply +
+add_relu); BasicBlock joins are one fused add+relu kernel.
 """
 from __future__ import annotations
 
@@ -15,7 +17,8 @@ import torch
 import torch.nn as nn
 
 from ...ops import BatchNorm2d, add_relu
-from ...ops.conv1x1 import conv_bn
+from ...ops.conv1x1 import (can_pass_input, conv1x1_bn, conv_bn,
+                            conv_bn_add_relu)
 from ..registry import register_model
 
 
@@ -101,12 +104,19 @@ class Bottleneck(nn.Module):
         # conv1/conv3 (1x1) ride the hand-written MFMA implicit-GEMM kernel
         # with the BN stats pass fused into the conv epilogue (conv1x1.hip);
         # conv2 (3x3) uses MIOpen by default (the TAPS=9 route is opt-in).
-        out = conv_bn(x, self.conv1, self.bn1)
+        if self.downsample is None and can_pass_input(x, self.conv1, self.bn1):
+            # the identity hangs off conv1's pass-through alias of x, so its
+            # gradient rides conv1's dgrad GEMM epilogue (no autograd add)
+            out, identity = conv1x1_bn(x, self.conv1, self.bn1,
+                                       pass_input=True)
+        else:
+            out = conv_bn(x, self.conv1, self.bn1)
         out = conv_bn(out, self.conv2, self.bn2)  # 3x3 s1 -> TAPS=9 kernel
-        out = conv_bn(out, self.conv3, self.bn3)
-        if self.downsample is not None:
-            identity = _downsample_fwd(self.downsample, x)
-        return add_relu(out, identity)
+        # conv3 -> bn3 -> (+identity | +downsample bn) -> relu: one join
+        # kernel after the conv GEMM(s) when the fused route applies, else
+        # conv_bn + add_relu as before
+        return conv_bn_add_relu(out, self.conv3, self.bn3, identity=identity,
+                                x_down=x, downsample=self.downsample)
 
 
 class ResNet(nn.Module):

@@ -1,6 +1,7 @@
 from ._ext import ext, has_ext, use_hip
 from .activations import GELU, SiLU, add_relu, gelu, silu
 from .batchnorm import BatchNorm2d, FrozenBatchNorm2d
+from .conv1x1 import conv1x1_bn, conv_bn, conv_bn_add_relu
 from .boxes import (batched_nms, bbox_iou_aligned, box_area, box_iou,
                     clip_boxes_to_image, generalized_box_iou, nms,
                     remove_small_boxes)
@@ -17,6 +18,7 @@ __all__ = [
     "ext", "has_ext", "use_hip",
     "gelu", "silu", "add_relu", "GELU", "SiLU",
     "BatchNorm2d", "FrozenBatchNorm2d",
+    "conv_bn", "conv1x1_bn", "conv_bn_add_relu",
     "box_iou", "generalized_box_iou", "bbox_iou_aligned", "box_area", "nms",
     "batched_nms", "clip_boxes_to_image", "remove_small_boxes",
     "DropPath", "drop_path", "ModelEMA",

@@ -38,11 +38,19 @@ class _Conv1x1Fn(torch.autograd.Function):
 
     Inputs are 2D bf16 (the NHWC flattening happens in the callers). The
     optional second output is the per-channel {sum, sumsq} of the raw conv
-    output (fp32 [2N]) for the downstream BatchNorm — non-differentiable.
+    output (fp32 [n_blocks, 2N] partial slab) for the downstream BatchNorm —
+    non-differentiable.
+
+    pass_input=True hands x2d back as a last, differentiable output (an
+    alias, not a copy). A residual branch hung off that alias delivers its
+    gradient to THIS node, which folds it into the dgrad GEMM's residual
+    epilogue (dx = dy @ W + d_alias in the store pass) — autograd no longer
+    sums the block input's two gradients with a separate add kernel.
     """
 
     @staticmethod
-    def forward(ctx, x2d, w, bias, scale, shift, residual, relu, want_stats):
+    def forward(ctx, x2d, w, bias, scale, shift, residual, relu, want_stats,
+                pass_input=False):
         xb = x2d if x2d.dtype == torch.bfloat16 else x2d.to(torch.bfloat16)
         wb = w if w.dtype == torch.bfloat16 else w.to(torch.bfloat16)
         wb = wb.contiguous()
@@ -51,22 +59,37 @@ class _Conv1x1Fn(torch.autograd.Function):
         ctx.save_for_backward(xb, wb)
         ctx.x_dtype = x2d.dtype
         ctx.w_dtype = w.dtype
+        ctx.pass_input = pass_input
+        outs = (y2d,)
         if want_stats:
             ctx.mark_non_differentiable(sums)
-            return y2d, sums
-        return y2d
+            outs += (sums,)
+        if pass_input:
+            # either branch may be unused downstream: receive None, not zeros
+            ctx.set_materialize_grads(False)
+            outs += (x2d,)
+        return outs if len(outs) > 1 else y2d
 
     @staticmethod
-    def backward(ctx, dy2d, *unused):
+    def backward(ctx, dy2d, *rest):
         xb, wb = ctx.saved_tensors
+        d_alias = rest[-1] if ctx.pass_input else None
+        if d_alias is not None:
+            d_alias = d_alias.contiguous()
+        dx = dw = db = None
+        if dy2d is None:  # only the pass-through output was used
+            if d_alias is not None and ctx.needs_input_grad[0]:
+                dx = d_alias.to(ctx.x_dtype)
+            return dx, None, None, None, None, None, None, None, None
         dy2d = dy2d.contiguous()
         if dy2d.dtype != torch.bfloat16:
             dy2d = dy2d.to(torch.bfloat16)
-        dx = dw = db = None
         if ctx.needs_input_grad[0]:
             # LDS-tiled transpose kernel (torch's strided copy is ~15x slower)
             wt = ext().transpose2d(wb)  # [K,N] bf16
-            dx, _ = ext().conv1x1_fwd(dy2d, wt, None, None, None, None,
+            if d_alias is not None and d_alias.dtype != torch.bfloat16:
+                d_alias = d_alias.to(torch.bfloat16)
+            dx, _ = ext().conv1x1_fwd(dy2d, wt, None, None, None, d_alias,
                                       False, False)
             if dx.dtype != ctx.x_dtype:
                 dx = dx.to(ctx.x_dtype)
@@ -164,19 +187,54 @@ def conv1x1(x: torch.Tensor, conv: nn.Conv2d) -> torch.Tensor:
     return _unflatten_nhwc(y2d, B, H, W)
 
 
-def conv1x1_bn(x: torch.Tensor, conv: nn.Conv2d, bn) -> torch.Tensor:
+def _fp32_running_stats(bn) -> None:
+    if bn.running_mean.dtype != torch.float32:
+        bn.running_mean.data = bn.running_mean.data.float()
+        bn.running_var.data = bn.running_var.data.float()
+
+
+def _conv1x1_train_stats(x: torch.Tensor, conv: nn.Conv2d, bn,
+                         pass_input: bool = False):
+    """Train-mode front half shared by conv1x1_bn and the fused join: conv
+    GEMM with the stats epilogue plus the BN bookkeeping. Returns (raw conv
+    output NHWC 4D, [n_blocks, 2C] stats partials, momentum, x alias|None)."""
+    x2d, wb, bias, (B, H, W) = _prep(x, conv)
+    _fp32_running_stats(bn)
+    if bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+    momentum = bn._eaf() if hasattr(bn, "_eaf") else (bn.momentum or 0.0)
+    outs = _Conv1x1Fn.apply(x2d, wb, bias, None, None, None, False, True,
+                            pass_input)
+    alias = _unflatten_nhwc(outs[2], B, H, W) if pass_input else None
+    return _unflatten_nhwc(outs[0], B, H, W), outs[1], momentum, alias
+
+
+def conv1x1_bn(x: torch.Tensor, conv: nn.Conv2d, bn,
+               pass_input: bool = False):
     """Fused conv1x1 + BatchNorm2d(+ReLU) chain.
 
     train: conv GEMM with fused channel-stats epilogue -> BN finalize+apply
            (skips the stats read pass over the conv output entirely)
     eval (no grad): ONE kernel — conv GEMM with scale/shift(+ReLU) epilogue.
+
+    pass_input=True (train, stride 1) returns (y, x_alias): route a residual
+    branch through x_alias and its gradient rides the dgrad GEMM epilogue.
     """
     relu = bool(getattr(bn, "relu", False))
-    x2d, wb, bias, (B, H, W) = _prep(x, conv)
+    if bn.training:
+        # conv + fused stats, then BN finalize/apply straight from the
+        # per-block partial slab
+        y_raw, partials, momentum, alias = _conv1x1_train_stats(
+            x, conv, bn, pass_input)
+        y = _BNFromStatsFn.apply(y_raw, bn.weight, bn.bias, partials,
+                                 bn.running_mean, bn.running_var, momentum,
+                                 bn.eps, relu)
+        return (y, alias) if pass_input else y
+    if pass_input:
+        raise ValueError("conv1x1_bn: pass_input needs train mode")
 
-    if bn.running_mean.dtype != torch.float32:
-        bn.running_mean.data = bn.running_mean.data.float()
-        bn.running_var.data = bn.running_var.data.float()
+    x2d, wb, bias, (B, H, W) = _prep(x, conv)
+    _fp32_running_stats(bn)
 
     if not bn.training:
         rstd = torch.rsqrt(bn.running_var + bn.eps)
@@ -197,17 +255,137 @@ def conv1x1_bn(x: torch.Tensor, conv: nn.Conv2d, bn) -> torch.Tensor:
             shift.reshape(1, -1, 1, 1).to(y.dtype)
         return torch.relu(y) if relu else y
 
-    # train: conv + fused stats, then BN finalize/apply
-    if bn.num_batches_tracked is not None:
-        bn.num_batches_tracked.add_(1)
-    momentum = bn._eaf() if hasattr(bn, "_eaf") else (bn.momentum or 0.0)
-    y2d, partials = _Conv1x1Fn.apply(x2d, wb, bias, None, None, None, False,
-                                     True)
-    sums = partials.sum(dim=0)  # [n_blocks, 2C] slab -> [2C]
-    y_raw = _unflatten_nhwc(y2d, B, H, W)
-    return _BNFromStatsFn.apply(y_raw, bn.weight, bn.bias, sums,
-                                bn.running_mean, bn.running_var, momentum,
-                                bn.eps, relu)
+
+class _BNJoinFn(torch.autograd.Function):
+    """out = relu(bn(x_raw) + identity) in one pass over memory; the BN is
+    finalized from the producing conv's stats partials and its output is
+    never materialised. Backward: pass 1 masks (g = dy*[out>0]) and reduces,
+    pass 2 writes dx_raw; the identity gradient is g itself."""
+
+    @staticmethod
+    def forward(ctx, x_raw, weight, bias, partials, running_mean,
+                running_var, momentum, eps, identity):
+        out, mean, rstd = ext().bn_add_relu_fwd_from_sums(
+            x_raw, weight, bias, partials, running_mean, running_var,
+            momentum, eps, identity)
+        ctx.save_for_backward(x_raw, out, weight, mean, rstd)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        x_raw, out, weight, mean, rstd = ctx.saved_tensors
+        g, dx, dw, db = ext().bn_add_relu_bwd(dy, out, x_raw, weight, mean,
+                                              rstd)
+        return dx, dw, db, None, None, None, None, None, g
+
+
+class _BNJoinDualFn(torch.autograd.Function):
+    """First block of a stage: out = relu(bn(x_raw) + bn_d(xd_raw)), both
+    operands raw conv outputs with their own BN (same C, same rows)."""
+
+    @staticmethod
+    def forward(ctx, x_raw, weight, bias, partials, running_mean,
+                running_var, momentum, eps, xd_raw, weight_d, bias_d,
+                partials_d, running_mean_d, running_var_d, momentum_d, eps_d):
+        out, mean, rstd, mean_d, rstd_d = \
+            ext().bn_add_relu_dual_fwd_from_sums(
+                x_raw, weight, bias, partials, running_mean, running_var,
+                momentum, eps, xd_raw, weight_d, bias_d, partials_d,
+                running_mean_d, running_var_d, momentum_d, eps_d)
+        ctx.save_for_backward(x_raw, xd_raw, out, weight, mean, rstd,
+                              weight_d, mean_d, rstd_d)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x_raw, xd_raw, out, weight, mean, rstd, weight_d, mean_d,
+         rstd_d) = ctx.saved_tensors
+        dx, dxd, dw, db, dwd, dbd = ext().bn_add_relu_dual_bwd(
+            dy, out, x_raw, weight, mean, rstd, xd_raw, weight_d, mean_d,
+            rstd_d)
+        return (dx, dw, db, None, None, None, None, None,
+                dxd, dwd, dbd, None, None, None, None, None)
+
+
+def _fused_join_disabled() -> bool:
+    return os.environ.get("DLA_NO_FUSED_JOIN", "0") == "1"  # A/B runs
+
+
+def _join_bn_ok(conv: nn.Conv2d, bn) -> bool:
+    from .batchnorm import BatchNorm2d
+
+    return (type(bn) is BatchNorm2d and bn.training and
+            not getattr(bn, "relu", False) and conv.bias is None)
+
+
+def can_pass_input(x: torch.Tensor, conv: nn.Conv2d, bn) -> bool:
+    """True when conv1x1_bn(x, conv, bn, pass_input=True) applies: the
+    identity gradient of a residual block can ride this conv's dgrad."""
+    from .batchnorm import BatchNorm2d
+
+    return (not _fused_join_disabled() and can_fuse_conv1x1(x, conv) and
+            conv.stride == (1, 1) and type(bn) is BatchNorm2d and
+            bn.training and torch.is_grad_enabled() and x.requires_grad)
+
+
+def can_fuse_join(x: torch.Tensor, conv: nn.Conv2d, bn, identity=None,
+                  x_down=None, downsample=None) -> bool:
+    """True when conv -> bn -> (+identity | +downsample(x_down)) -> relu can
+    run as conv+stats GEMM(s) and ONE join kernel."""
+    if _fused_join_disabled() or not can_fuse_conv1x1(x, conv) or \
+            not _join_bn_ok(conv, bn):
+        return False
+    if downsample is not None:
+        if not (isinstance(downsample, nn.Sequential) and
+                len(downsample) == 2 and
+                isinstance(downsample[0], nn.Conv2d)):
+            return False
+        return (x_down is not None and
+                can_fuse_conv1x1(x_down, downsample[0]) and
+                _join_bn_ok(downsample[0], downsample[1]) and
+                downsample[0].out_channels == conv.out_channels)
+    return (identity is not None and use_hip(identity) and
+            identity.dtype == torch.bfloat16 and identity.dim() == 4 and
+            identity.is_contiguous(memory_format=torch.channels_last))
+
+
+def conv_bn_add_relu(x: torch.Tensor, conv: nn.Conv2d, bn, identity=None,
+                     x_down=None, downsample=None) -> torch.Tensor:
+    """The residual join relu(bn(conv(x)) + branch), where branch is
+    `identity`, or `downsample(x_down)` when a downsample module is given.
+
+    Fused route (GPU, bf16, channels_last, channels % 64, train-mode
+    BatchNorm2d, 1x1 convs): conv GEMM(s) with stats epilogue, then one
+    kernel that finalizes, normalises, adds and applies ReLU. Anything else
+    runs the plain composition conv_bn -> add_relu."""
+    if can_fuse_join(x, conv, bn, identity, x_down, downsample):
+        y_raw, partials, momentum, _ = _conv1x1_train_stats(x, conv, bn)
+        if downsample is None:
+            if identity.shape != y_raw.shape:
+                raise ValueError("conv_bn_add_relu: identity shape mismatch")
+            return _BNJoinFn.apply(y_raw, bn.weight, bn.bias, partials,
+                                   bn.running_mean, bn.running_var, momentum,
+                                   bn.eps, identity)
+        conv_d, bn_d = downsample[0], downsample[1]
+        yd_raw, partials_d, momentum_d, _ = _conv1x1_train_stats(
+            x_down, conv_d, bn_d)
+        if yd_raw.shape != y_raw.shape:
+            raise ValueError("conv_bn_add_relu: downsample shape mismatch")
+        return _BNJoinDualFn.apply(
+            y_raw, bn.weight, bn.bias, partials, bn.running_mean,
+            bn.running_var, momentum, bn.eps, yd_raw, bn_d.weight, bn_d.bias,
+            partials_d, bn_d.running_mean, bn_d.running_var, momentum_d,
+            bn_d.eps)
+    from .activations import add_relu
+
+    out = conv_bn(x, conv, bn)
+    if downsample is not None:
+        if (isinstance(downsample, nn.Sequential) and len(downsample) == 2
+                and isinstance(downsample[0], nn.Conv2d)):
+            identity = conv_bn(x_down, downsample[0], downsample[1])
+        else:
+            identity = downsample(x_down)
+    return add_relu(out, identity)
 
 
 def conv_bn(x: torch.Tensor, conv: nn.Conv2d, bn) -> torch.Tensor:
@@ -333,7 +511,6 @@ def conv3x3_bn(x: torch.Tensor, conv: nn.Conv2d, bn) -> torch.Tensor:
         bn.num_batches_tracked.add_(1)
     momentum = bn._eaf() if hasattr(bn, "_eaf") else (bn.momentum or 0.0)
     y_raw, partials = _Conv3x3Fn.apply(x, conv.weight, True)
-    sums = partials.sum(dim=0)
-    return _BNFromStatsFn.apply(y_raw, bn.weight, bn.bias, sums,
+    return _BNFromStatsFn.apply(y_raw, bn.weight, bn.bias, partials,
                                 bn.running_mean, bn.running_var, momentum,
                                 bn.eps, relu)
