@@ -10,6 +10,21 @@
 
 namespace dla {
 
+// The BN pre-activation x*scale + shift as ONE explicit fused multiply-add.
+// The forward apply kernels and the ReLU mask of the backward kernels both go
+// through this function, so the mask `bn_pre(x, sc, sh) > 0` is decided by the
+// very instruction sequence that produced y.
+//
+// Known edge of masking from x and not from the stored y: the two differ
+// only where a positive fp32 pre-activation rounds to zero in the storage
+// type. bf16 has fp32's exponent range, so that needs a value below bf16's
+// smallest subnormal (~9e-41); for fp16 it is anything below ~3e-8. A NaN
+// pre-activation gives mask 0 on both routes (fmaxf(NaN, 0) = 0 forward,
+// NaN > 0 false backward).
+__device__ __forceinline__ float bn_pre(float x, float sc, float sh) {
+  return fmaf(x, sc, sh);
+}
+
 // ---- pass 1: per-channel sum / sumsq ---------------------------------------
 template <typename dev_t>
 __global__ void bn_stats_kernel(const dev_t* __restrict__ x, float* __restrict__ sums,
@@ -129,7 +144,7 @@ __global__ void bn_apply_kernel(const dev_t* __restrict__ x,
     Vec<dev_t, V> yv;
 #pragma unroll
     for (int j = 0; j < V; ++j) {
-      float f = to_f32(xv.v[j]) * sc + sh;
+      const float f = bn_pre(to_f32(xv.v[j]), sc, sh);
       yv.v[j] = from_f32<dev_t>(RELU ? fmaxf(f, 0.f) : f);
     }
     vstore<dev_t, V>(y + i, yv);
@@ -266,17 +281,22 @@ __global__ void bn_apply_nhwc_kernel(const dev_t* __restrict__ x,
     Vec<dev_t, V> yv;
 #pragma unroll
     for (int j = 0; j < V; ++j) {
-      const float f = to_f32(xv.v[j]) * sc[j] + sh[j];
+      const float f = bn_pre(to_f32(xv.v[j]), sc[j], sh[j]);
       yv.v[j] = from_f32<dev_t>(RELU ? fmaxf(f, 0.f) : f);
     }
     vstore<dev_t, V>(y + r * C + c0, yv);
   }
 }
 
-template <typename dev_t, int V, bool RELU>
+// RELU backward kernels take the mask from x (MASK_Y = false: g = 0 where
+// bn_pre(x, scale, shift) is not > 0; y is neither passed nor loaded) or, for
+// A/B runs and callers of the old entry point, from the stored y (MASK_Y).
+template <typename dev_t, int V, bool RELU, bool MASK_Y = false>
 __global__ void bn_bwd_stats_nhwc_kernel(const dev_t* __restrict__ dy,
                                          const dev_t* __restrict__ x,
                                          const dev_t* __restrict__ y,
+                                         const float* __restrict__ scale,
+                                         const float* __restrict__ shift,
                                          const float* __restrict__ mean,
                                          const float* __restrict__ rstd,
                                          float* __restrict__ sums, int C,
@@ -289,11 +309,13 @@ __global__ void bn_bwd_stats_nhwc_kernel(const dev_t* __restrict__ dy,
   if (t < used) {
     const int c0 = (int)(t % lanes_per_row) * V;
     const int64_t rstride = used / lanes_per_row;
-    float mu[V], rs[V], s_dy[V], s_dyxh[V];
+    float mu[V], rs[V], sc[V], sh[V], s_dy[V], s_dyxh[V];
 #pragma unroll
     for (int j = 0; j < V; ++j) {
       mu[j] = mean[c0 + j];
       rs[j] = rstd[c0 + j];
+      sc[j] = (RELU && !MASK_Y) ? scale[c0 + j] : 0.f;
+      sh[j] = (RELU && !MASK_Y) ? shift[c0 + j] : 0.f;
       s_dy[j] = 0.f;
       s_dyxh[j] = 0.f;
     }
@@ -302,12 +324,14 @@ __global__ void bn_bwd_stats_nhwc_kernel(const dev_t* __restrict__ dy,
       Vec<dev_t, V> dyv = vload<dev_t, V>(dy + base);
       Vec<dev_t, V> xv = vload<dev_t, V>(x + base);
       Vec<dev_t, V> yv;
-      if (RELU) yv = vload<dev_t, V>(y + base);
+      if (RELU && MASK_Y) yv = vload<dev_t, V>(y + base);
 #pragma unroll
       for (int j = 0; j < V; ++j) {
         float g = to_f32(dyv.v[j]);
-        if (RELU && to_f32(yv.v[j]) <= 0.f) g = 0.f;
-        const float xh = (to_f32(xv.v[j]) - mu[j]) * rs[j];
+        const float xf = to_f32(xv.v[j]);
+        if (RELU && MASK_Y && to_f32(yv.v[j]) <= 0.f) g = 0.f;
+        if (RELU && !MASK_Y && !(bn_pre(xf, sc[j], sh[j]) > 0.f)) g = 0.f;
+        const float xh = (xf - mu[j]) * rs[j];
         s_dy[j] += g;
         s_dyxh[j] += g * xh;
       }
@@ -323,10 +347,12 @@ __global__ void bn_bwd_stats_nhwc_kernel(const dev_t* __restrict__ dy,
     atomicAdd(&sums[i], ls[i]);
 }
 
-template <typename dev_t, int V, bool RELU>
+template <typename dev_t, int V, bool RELU, bool MASK_Y = false>
 __global__ void bn_bwd_dx_nhwc_kernel(const dev_t* __restrict__ dy,
                                       const dev_t* __restrict__ x,
                                       const dev_t* __restrict__ y,
+                                      const float* __restrict__ scale,
+                                      const float* __restrict__ shift,
                                       const float* __restrict__ mean,
                                       const float* __restrict__ rstd,
                                       const float* __restrict__ weight,
@@ -339,12 +365,14 @@ __global__ void bn_bwd_dx_nhwc_kernel(const dev_t* __restrict__ dy,
   const int lanes_per_row = C / V;
   const int c0 = (int)(t % lanes_per_row) * V;
   const int64_t rstride = used / lanes_per_row;
-  float mu[V], rs[V], wr[V], m_dy[V], m_dyxh[V];
+  float mu[V], rs[V], wr[V], sc[V], sh[V], m_dy[V], m_dyxh[V];
 #pragma unroll
   for (int j = 0; j < V; ++j) {
     mu[j] = mean[c0 + j];
     rs[j] = rstd[c0 + j];
     wr[j] = weight[c0 + j] * rs[j];
+    sc[j] = (RELU && !MASK_Y) ? scale[c0 + j] : 0.f;
+    sh[j] = (RELU && !MASK_Y) ? shift[c0 + j] : 0.f;
     m_dy[j] = sums[c0 + j] * inv_count;
     m_dyxh[j] = sums[C + c0 + j] * inv_count;
   }
@@ -353,13 +381,15 @@ __global__ void bn_bwd_dx_nhwc_kernel(const dev_t* __restrict__ dy,
     Vec<dev_t, V> dyv = vload<dev_t, V>(dy + base);
     Vec<dev_t, V> xv = vload<dev_t, V>(x + base);
     Vec<dev_t, V> yv;
-    if (RELU) yv = vload<dev_t, V>(y + base);
+    if (RELU && MASK_Y) yv = vload<dev_t, V>(y + base);
     Vec<dev_t, V> dxv;
 #pragma unroll
     for (int j = 0; j < V; ++j) {
       float g = to_f32(dyv.v[j]);
-      if (RELU && to_f32(yv.v[j]) <= 0.f) g = 0.f;
-      const float xh = (to_f32(xv.v[j]) - mu[j]) * rs[j];
+      const float xf = to_f32(xv.v[j]);
+      if (RELU && MASK_Y && to_f32(yv.v[j]) <= 0.f) g = 0.f;
+      if (RELU && !MASK_Y && !(bn_pre(xf, sc[j], sh[j]) > 0.f)) g = 0.f;
+      const float xh = (xf - mu[j]) * rs[j];
       dxv.v[j] = from_f32<dev_t>(wr[j] * (g - m_dy[j] - xh * m_dyxh[j]));
     }
     vstore<dev_t, V>(dx + r * C + c0, dxv);
@@ -586,7 +616,9 @@ inline bool is_nhwc_rows(const torch::Tensor& t) {
 
 }  // namespace dla
 
-// Returns {y, save_mean, save_rstd}. Updates running stats in-place when given.
+// Returns {y, save_mean, save_rstd, scale, shift}; scale/shift are the
+// per-channel fp32 coefficients of the apply pass, which the backward's
+// mask-from-x route needs again. Updates running stats in-place when given.
 std::vector<torch::Tensor> batchnorm_fwd(torch::Tensor x, torch::Tensor weight,
                                          torch::Tensor bias,
                                          c10::optional<torch::Tensor> running_mean,
@@ -674,7 +706,7 @@ std::vector<torch::Tensor> batchnorm_fwd(torch::Tensor x, torch::Tensor weight,
     }
   });
   HIP_CHECK_ERR();
-  return {y, mean, rstd};
+  return {y, mean, rstd, scale, shift};
 }
 
 // Train-mode BN forward with the stats pass ALREADY DONE by the producing
@@ -735,7 +767,7 @@ std::vector<torch::Tensor> batchnorm_fwd_from_sums(
     }
   });
   HIP_CHECK_ERR();
-  return {y, mean, rstd};
+  return {y, mean, rstd, scale, shift};
 }
 
 // Frozen/eval BN apply (+optional ReLU): per-channel scale/shift precomputed host-side.
@@ -788,11 +820,20 @@ torch::Tensor bn_apply(torch::Tensor x, torch::Tensor scale, torch::Tensor shift
   return y;
 }
 
-// Returns {dx, dweight, dbias}. y is required when relu=true (mask source).
-std::vector<torch::Tensor> batchnorm_bwd(torch::Tensor dy, torch::Tensor x,
-                                         c10::optional<torch::Tensor> y,
-                                         torch::Tensor weight, torch::Tensor mean,
-                                         torch::Tensor rstd, bool relu) {
+// The one rule for where the ReLU mask of a BN(+ReLU) backward comes from:
+// channels-last x takes it from x (bn_pre(x, scale, shift) > 0, no y read);
+// NCHW x keeps reading the stored y. The Python autograd functions ask this
+// same function in forward to decide whether y has to be saved.
+bool bn_relu_mask_from_x(torch::Tensor x) { return dla::is_nhwc(x); }
+
+// Returns {dx, dweight, dbias}. relu=true needs a mask source: the forward's
+// scale and shift (channels-last only, see bn_relu_mask_from_x), or else y.
+// When y is given it is used, so the old signature keeps its meaning.
+std::vector<torch::Tensor> batchnorm_bwd_ex(
+    torch::Tensor dy, torch::Tensor x, c10::optional<torch::Tensor> y,
+    torch::Tensor weight, torch::Tensor mean, torch::Tensor rstd,
+    c10::optional<torch::Tensor> scale, c10::optional<torch::Tensor> shift,
+    bool relu) {
   DLA_CHECK_CUDA(dy); DLA_CHECK_CUDA(x);
   const bool nhwc = dla::is_nhwc(x);
   TORCH_CHECK(nhwc || x.is_contiguous(), "batchnorm_bwd: x must be contiguous");
@@ -807,11 +848,33 @@ std::vector<torch::Tensor> batchnorm_bwd(torch::Tensor dy, torch::Tensor x,
   auto w32 = weight.to(torch::kFloat);
   const int ysplit = (int)std::min<int64_t>((rows + 65535) / 65536 + 1,
                                             std::max(1, 2048 / C));
-  TORCH_CHECK(!relu || y.has_value(), "batchnorm_bwd: relu mask needs y");
+  const bool mask_y = relu && y.has_value();
+  if (relu && !mask_y) {
+    TORCH_CHECK(bn_relu_mask_from_x(x) && scale.has_value() && shift.has_value(),
+                "batchnorm_bwd: the relu mask needs y, or channels_last x "
+                "with the forward's scale and shift");
+    for (const auto* t : {&*scale, &*shift})
+      TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kFloat &&
+                      t->is_contiguous() && t->numel() == C,
+                  "batchnorm_bwd: scale/shift must be contiguous fp32 [C]");
+  }
+  if (mask_y)
+    TORCH_CHECK(y->scalar_type() == x.scalar_type() && y->sizes() == x.sizes() &&
+                    (nhwc ? dla::is_nhwc(*y) : y->is_contiguous()),
+                "batchnorm_bwd: y must match x (shape, dtype, layout)");
+  const float* scp = (relu && !mask_y) ? scale->data_ptr<float>() : nullptr;
+  const float* shp = (relu && !mask_y) ? shift->data_ptr<float>() : nullptr;
   DLA_DISPATCH_FLOAT_TYPES(x.scalar_type(), "batchnorm_bwd", [&] {
-    const dev_t* yp = y.has_value() ? (const dev_t*)y->data_ptr() : nullptr;
-    auto launch_stats = [&](auto rtag) {
+    const dev_t* yp = mask_y ? (const dev_t*)y->data_ptr() : nullptr;
+    // (RELU, MASK_Y) as compile-time tags: (false,false), (true,false), (true,true)
+    auto with_mode = [&](auto f) {
+      if (!relu) f(std::false_type{}, std::false_type{});
+      else if (mask_y) f(std::true_type{}, std::true_type{});
+      else f(std::true_type{}, std::false_type{});
+    };
+    with_mode([&](auto rtag, auto mtag) {
       constexpr bool R = decltype(rtag)::value;
+      constexpr bool MY = decltype(mtag)::value;
       if (nhwc) {
         constexpr int VM = 16 / (int)sizeof(dev_t);
         auto stats = [&](auto vtag) {
@@ -819,43 +882,46 @@ std::vector<torch::Tensor> batchnorm_bwd(torch::Tensor dy, torch::Tensor x,
           const int lanes = C / V;
           const int64_t used = dla::nhwc_used_threads(lanes, rows, 262144);
           const int lds = 2 * C * sizeof(float);
-          hipLaunchKernelGGL((dla::bn_bwd_stats_nhwc_kernel<dev_t, V, R>),
+          hipLaunchKernelGGL((dla::bn_bwd_stats_nhwc_kernel<dev_t, V, R, MY>),
                              dim3((int)((used + 255) / 256)), dim3(256), lds,
                              dla::stream(), (const dev_t*)dy.data_ptr(),
-                             (const dev_t*)x.data_ptr(), yp, mean.data_ptr<float>(),
-                             rstd.data_ptr<float>(), sums.data_ptr<float>(), C,
-                             rows, used);
+                             (const dev_t*)x.data_ptr(), yp, scp, shp,
+                             mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                             sums.data_ptr<float>(), C, rows, used);
         };
         if (C % VM == 0) stats(std::integral_constant<int, VM>{});
         else if (C % 2 == 0) stats(std::integral_constant<int, 2>{});
         else stats(std::integral_constant<int, 1>{});
-      } else {
+      } else if constexpr (!R || MY) {
         hipLaunchKernelGGL((dla::bn_bwd_stats_kernel<dev_t, R>), dim3(C, ysplit),
                            dim3(256), 0, dla::stream(), (const dev_t*)dy.data_ptr(),
                            (const dev_t*)x.data_ptr(), yp, mean.data_ptr<float>(),
                            rstd.data_ptr<float>(), sums.data_ptr<float>(), N, C, HW);
       }
-    };
-    if (relu) launch_stats(std::true_type{});
-    else launch_stats(std::false_type{});
+    });
 
     const int64_t n_total = x.numel();
     const float inv_count = 1.f / (float)rows;
     constexpr int VMAX = 16 / (int)sizeof(dev_t);
-    auto launch_dx = [&](auto vtag, auto rtag) {
-      constexpr int V = decltype(vtag)::value;
+    with_mode([&](auto rtag, auto mtag) {
       constexpr bool R = decltype(rtag)::value;
+      constexpr bool MY = decltype(mtag)::value;
       if (nhwc) {
-        const int lanes = C / V;
-        const int64_t used = dla::nhwc_used_threads(lanes, rows, 524288);
-        hipLaunchKernelGGL((dla::bn_bwd_dx_nhwc_kernel<dev_t, V, R>),
-                           dim3((int)((used + 255) / 256)), dim3(256), 0,
-                           dla::stream(), (const dev_t*)dy.data_ptr(),
-                           (const dev_t*)x.data_ptr(), yp, mean.data_ptr<float>(),
-                           rstd.data_ptr<float>(), w32.data_ptr<float>(),
-                           sums.data_ptr<float>(), (dev_t*)dx.data_ptr(), C,
-                           rows, used, inv_count);
-      } else {
+        auto dxk = [&](auto vtag) {
+          constexpr int V = decltype(vtag)::value;
+          const int lanes = C / V;
+          const int64_t used = dla::nhwc_used_threads(lanes, rows, 524288);
+          hipLaunchKernelGGL((dla::bn_bwd_dx_nhwc_kernel<dev_t, V, R, MY>),
+                             dim3((int)((used + 255) / 256)), dim3(256), 0,
+                             dla::stream(), (const dev_t*)dy.data_ptr(),
+                             (const dev_t*)x.data_ptr(), yp, scp, shp,
+                             mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                             w32.data_ptr<float>(), sums.data_ptr<float>(),
+                             (dev_t*)dx.data_ptr(), C, rows, used, inv_count);
+        };
+        if (C % VMAX == 0) dxk(std::integral_constant<int, VMAX>{});
+        else dxk(std::integral_constant<int, 1>{});
+      } else if constexpr (!R || MY) {
         hipLaunchKernelGGL((dla::bn_bwd_dx_kernel<dev_t, R>), dim3(dla::grid_1d(n_total, 256)),
                            dim3(256), 0, dla::stream(), (const dev_t*)dy.data_ptr(),
                            (const dev_t*)x.data_ptr(), yp, mean.data_ptr<float>(),
@@ -863,19 +929,21 @@ std::vector<torch::Tensor> batchnorm_bwd(torch::Tensor dy, torch::Tensor x,
                            sums.data_ptr<float>(), (dev_t*)dx.data_ptr(), C, HW,
                            n_total, inv_count);
       }
-    };
-    const bool vec_ok = nhwc && (C % VMAX == 0);
-    if (vec_ok) {
-      if (relu) launch_dx(std::integral_constant<int, VMAX>{}, std::true_type{});
-      else launch_dx(std::integral_constant<int, VMAX>{}, std::false_type{});
-    } else {
-      if (relu) launch_dx(std::integral_constant<int, 1>{}, std::true_type{});
-      else launch_dx(std::integral_constant<int, 1>{}, std::false_type{});
-    }
+    });
   });
   HIP_CHECK_ERR();
   return {dx, dla::bn_param_grad(sums, C, C, weight),
           dla::bn_param_grad(sums, 0, C, weight)};
+}
+
+// Today's signature: the mask comes from y.
+std::vector<torch::Tensor> batchnorm_bwd(torch::Tensor dy, torch::Tensor x,
+                                         c10::optional<torch::Tensor> y,
+                                         torch::Tensor weight, torch::Tensor mean,
+                                         torch::Tensor rstd, bool relu) {
+  TORCH_CHECK(!relu || y.has_value(), "batchnorm_bwd: relu mask needs y");
+  return batchnorm_bwd_ex(dy, x, relu ? y : c10::nullopt, weight, mean, rstd,
+                          c10::nullopt, c10::nullopt, relu);
 }
 
 // ---- fused residual join ----------------------------------------------------
@@ -999,7 +1067,7 @@ std::vector<torch::Tensor> bn_add_relu_bwd(torch::Tensor dy, torch::Tensor out,
     hipLaunchKernelGGL((dla::bn_bwd_dx_nhwc_kernel<dev_t, V, false>),
                        dim3((int)((used + 255) / 256)), dim3(256), 0,
                        dla::stream(), (const dev_t*)g.data_ptr(),
-                       (const dev_t*)x.data_ptr(), nullptr,
+                       (const dev_t*)x.data_ptr(), nullptr, nullptr, nullptr,
                        mean.data_ptr<float>(), rstd.data_ptr<float>(),
                        w32.data_ptr<float>(), sums.data_ptr<float>(),
                        (dev_t*)dx.data_ptr(), C, rows, used,
@@ -1067,4 +1135,321 @@ std::vector<torch::Tensor> bn_add_relu_dual_bwd(
   return {dx, dxd, dla::bn_param_grad(sums, C, C, weight), dbias,
           dla::bn_param_grad(sums, 2 * C, C, weight_d),
           dbias.to(weight_d.scalar_type()).clone()};
+}
+
+// ---- fused stem: BN apply + ReLU + 3x3 / stride 2 / pad 1 max-pool ----------
+// pooled = max_pool(T(relu(bn_pre(x)))) over the raw conv output x (NHWC), T
+// the rounding to the storage type. The BN output y is never written: rounding
+// and ReLU are monotone, so the maximum of the rounded values is the value the
+// unfused route pools, bit for bit. Instead of aten's int64 indices the kernel
+// keeps one uint8 slot (kh*3 + kw, 0..8) per pooled element: the first maximum
+// in row-major window order wins (aten's `val > maxval`), padding positions
+// never take part.
+namespace dla {
+
+constexpr int kPoolRun = 8;  // consecutive output rows of one image per block
+
+// One block owns kPoolRun consecutive output rows of one image, so the input
+// rows that neighbouring windows share are re-read from this CU's caches and
+// only the one row shared with the next run is fetched twice.
+template <typename dev_t, int V>
+__global__ void __launch_bounds__(256)
+bn_relu_maxpool_fwd_nhwc_kernel(const dev_t* __restrict__ x,
+                                const float* __restrict__ scale,
+                                const float* __restrict__ shift,
+                                dev_t* __restrict__ out,
+                                uint8_t* __restrict__ slots, int C, int H,
+                                int W, int OH, int OW, int runs_per_img) {
+  const int n = blockIdx.x / runs_per_img;
+  const int oh0 = (blockIdx.x % runs_per_img) * kPoolRun;
+  const int oh1 = min(oh0 + kPoolRun, OH);
+  const int lanes = C / V;
+  const int items = (oh1 - oh0) * OW * lanes;
+  const dev_t* xn = x + (int64_t)n * H * W * C;
+  const int64_t obase = ((int64_t)n * OH + oh0) * OW * C;
+  for (int i = threadIdx.x; i < items; i += blockDim.x) {
+    const int c0 = (i % lanes) * V;
+    const int p = i / lanes;  // output pixel within the run
+    const int ow = p % OW, oh = oh0 + p / OW;
+    float sc[V], sh[V], best[V];
+    int slot[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      sc[j] = scale[c0 + j];
+      sh[j] = shift[c0 + j];
+      best[j] = -INFINITY;
+      slot[j] = 4;  // the window centre is always inside the image
+    }
+#pragma unroll
+    for (int kh = 0; kh < 3; ++kh) {
+      const int ih = 2 * oh - 1 + kh;
+      if (ih < 0 || ih >= H) continue;
+#pragma unroll
+      for (int kw = 0; kw < 3; ++kw) {
+        const int iw = 2 * ow - 1 + kw;
+        if (iw < 0 || iw >= W) continue;
+        Vec<dev_t, V> xv =
+            vload<dev_t, V>(xn + ((int64_t)ih * W + iw) * C + c0);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+          const float f = bn_pre(to_f32(xv.v[j]), sc[j], sh[j]);
+          const float y = to_f32(from_f32<dev_t>(fmaxf(f, 0.f)));
+          if (y > best[j]) {
+            best[j] = y;
+            slot[j] = kh * 3 + kw;
+          }
+        }
+      }
+    }
+    Vec<dev_t, V> ov;
+    Vec<uint8_t, V> sv;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      ov.v[j] = from_f32<dev_t>(best[j]);  // exact: best is a dev_t value
+      sv.v[j] = (uint8_t)slot[j];
+    }
+    const int64_t o = obase + (int64_t)p * C + c0;
+    vstore<dev_t, V>(out + o, ov);
+    vstore<uint8_t, V>(slots + o, sv);
+  }
+}
+
+// Gradient reaching the BN output at input position (n, h, w), channels
+// c0..c0+V-1, in fp32: the dpool values of the at most four windows that
+// cover (h, w) and whose slot points at it, summed in the fixed order (oh, ow)
+// ascending, then zeroed under the ReLU mask taken from x. Both backward
+// kernels gather through this function, so neither writes a full-size g and
+// nothing is scattered with atomics.
+template <typename dev_t, int V>
+__device__ __forceinline__ void stem_pool_grad(
+    const dev_t* __restrict__ dpool, const uint8_t* __restrict__ slots,
+    const Vec<dev_t, V>& xv, const float* sc, const float* sh, int n, int h,
+    int w, int c0, int C, int OH, int OW, float* g) {
+#pragma unroll
+  for (int j = 0; j < V; ++j) g[j] = 0.f;
+  // rows/columns 2k are covered by window k only, 2k+1 by windows k and k+1
+  const int oh_hi = min((h + 1) >> 1, OH - 1);
+  const int ow_hi = min((w + 1) >> 1, OW - 1);
+  for (int oh = h >> 1; oh <= oh_hi; ++oh) {
+    const int kh = h - 2 * oh + 1;
+    for (int ow = w >> 1; ow <= ow_hi; ++ow) {
+      const int want = kh * 3 + (w - 2 * ow + 1);
+      const int64_t o = (((int64_t)n * OH + oh) * OW + ow) * C + c0;
+      Vec<uint8_t, V> sv = vload<uint8_t, V>(slots + o);
+      Vec<dev_t, V> dv = vload<dev_t, V>(dpool + o);
+#pragma unroll
+      for (int j = 0; j < V; ++j)
+        if ((int)sv.v[j] == want) g[j] += to_f32(dv.v[j]);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < V; ++j)
+    if (!(bn_pre(to_f32(xv.v[j]), sc[j], sh[j]) > 0.f)) g[j] = 0.f;
+}
+
+// Backward pass 1: sum g, sum g*xhat per channel; thread mapping and the
+// LDS-then-global-atomics reduction are bn_bwd_stats_nhwc_kernel's.
+template <typename dev_t, int V>
+__global__ void bn_relu_maxpool_bwd_stats_nhwc_kernel(
+    const dev_t* __restrict__ dpool, const uint8_t* __restrict__ slots,
+    const dev_t* __restrict__ x, const float* __restrict__ scale,
+    const float* __restrict__ shift, const float* __restrict__ mean,
+    const float* __restrict__ rstd, float* __restrict__ sums, int C, int H,
+    int W, int OH, int OW, int64_t rows, int64_t used) {
+  extern __shared__ float ls[];
+  for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) ls[i] = 0.f;
+  __syncthreads();
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int lanes_per_row = C / V;
+  if (t < used) {
+    const int c0 = (int)(t % lanes_per_row) * V;
+    const int64_t rstride = used / lanes_per_row;
+    float mu[V], rs[V], sc[V], sh[V], s_g[V], s_gxh[V], g[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      mu[j] = mean[c0 + j];
+      rs[j] = rstd[c0 + j];
+      sc[j] = scale[c0 + j];
+      sh[j] = shift[c0 + j];
+      s_g[j] = 0.f;
+      s_gxh[j] = 0.f;
+    }
+    for (int64_t r = t / lanes_per_row; r < rows; r += rstride) {
+      const uint32_t r32 = (uint32_t)r;  // rows < 2^31 (checked by the host)
+      const uint32_t q = r32 / (uint32_t)W;
+      const int w = (int)(r32 - q * (uint32_t)W);
+      const int n = (int)(q / (uint32_t)H);
+      const int h = (int)(q - (uint32_t)n * (uint32_t)H);
+      Vec<dev_t, V> xv = vload<dev_t, V>(x + r * C + c0);
+      stem_pool_grad<dev_t, V>(dpool, slots, xv, sc, sh, n, h, w, c0, C, OH,
+                               OW, g);
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        const float xh = (to_f32(xv.v[j]) - mu[j]) * rs[j];
+        s_g[j] += g[j];
+        s_gxh[j] += g[j] * xh;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      atomicAdd(&ls[c0 + j], s_g[j]);
+      atomicAdd(&ls[C + c0 + j], s_gxh[j]);
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 2 * C; i += blockDim.x)
+    atomicAdd(&sums[i], ls[i]);
+}
+
+// Backward pass 2: dx = weight*rstd*(g - mean(g) - xhat*mean(g*xhat)).
+template <typename dev_t, int V>
+__global__ void bn_relu_maxpool_bwd_dx_nhwc_kernel(
+    const dev_t* __restrict__ dpool, const uint8_t* __restrict__ slots,
+    const dev_t* __restrict__ x, const float* __restrict__ scale,
+    const float* __restrict__ shift, const float* __restrict__ mean,
+    const float* __restrict__ rstd, const float* __restrict__ weight,
+    const float* __restrict__ sums, dev_t* __restrict__ dx, int C, int H,
+    int W, int OH, int OW, int64_t rows, int64_t used, float inv_count) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= used) return;
+  const int lanes_per_row = C / V;
+  const int c0 = (int)(t % lanes_per_row) * V;
+  const int64_t rstride = used / lanes_per_row;
+  float mu[V], rs[V], wr[V], sc[V], sh[V], m_g[V], m_gxh[V], g[V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) {
+    mu[j] = mean[c0 + j];
+    rs[j] = rstd[c0 + j];
+    wr[j] = weight[c0 + j] * rs[j];
+    sc[j] = scale[c0 + j];
+    sh[j] = shift[c0 + j];
+    m_g[j] = sums[c0 + j] * inv_count;
+    m_gxh[j] = sums[C + c0 + j] * inv_count;
+  }
+  for (int64_t r = t / lanes_per_row; r < rows; r += rstride) {
+    const uint32_t r32 = (uint32_t)r;  // rows < 2^31 (checked by the host)
+    const uint32_t q = r32 / (uint32_t)W;
+    const int w = (int)(r32 - q * (uint32_t)W);
+    const int n = (int)(q / (uint32_t)H);
+    const int h = (int)(q - (uint32_t)n * (uint32_t)H);
+    Vec<dev_t, V> xv = vload<dev_t, V>(x + r * C + c0);
+    stem_pool_grad<dev_t, V>(dpool, slots, xv, sc, sh, n, h, w, c0, C, OH, OW,
+                             g);
+    Vec<dev_t, V> dxv;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      const float xh = (to_f32(xv.v[j]) - mu[j]) * rs[j];
+      dxv.v[j] = from_f32<dev_t>(wr[j] * (g[j] - m_g[j] - xh * m_gxh[j]));
+    }
+    vstore<dev_t, V>(dx + r * C + c0, dxv);
+  }
+}
+
+inline void stem_check(const torch::Tensor& x, const char* fn) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4 && is_nhwc_rows(x), fn,
+              ": x must be a channels_last 4D GPU tensor");
+  const int vmax = 16 / (int)x.element_size();
+  TORCH_CHECK(x.size(1) % vmax == 0, fn, ": C must be a multiple of ", vmax);
+  TORCH_CHECK(x.numel() > 0 && x.numel() / x.size(1) < (int64_t(1) << 31),
+              fn, ": N*H*W must be in [1, 2^31)");
+}
+
+}  // namespace dla
+
+// Train-mode stem. Returns {pooled, slots (uint8), mean, rstd, scale, shift};
+// running stats are updated in place when given.
+std::vector<torch::Tensor> bn_relu_maxpool_fwd(
+    torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
+    c10::optional<torch::Tensor> running_mean,
+    c10::optional<torch::Tensor> running_var, double momentum, double eps) {
+  dla::stem_check(x, "bn_relu_maxpool_fwd");
+  const int N = (int)x.size(0), C = (int)x.size(1);
+  const int H = (int)x.size(2), W = (int)x.size(3);
+  const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
+  const int64_t rows = (int64_t)N * H * W;
+  auto sums = torch::zeros({2 * C}, x.options().dtype(torch::kFloat));
+  auto out_opts = x.options().memory_format(at::MemoryFormat::ChannelsLast);
+  auto pooled = torch::empty({N, C, OH, OW}, out_opts);
+  auto slots = torch::empty({N, C, OH, OW}, out_opts.dtype(torch::kByte));
+  const int runs = (OH + dla::kPoolRun - 1) / dla::kPoolRun;
+  TORCH_CHECK((int64_t)N * runs < (int64_t(1) << 31),
+              "bn_relu_maxpool_fwd: too many blocks");
+  dla::BnFinalized fin;
+  DLA_DISPATCH_FLOAT_TYPES(x.scalar_type(), "bn_relu_maxpool_fwd", [&] {
+    constexpr int V = 16 / (int)sizeof(dev_t);
+    const int64_t used = dla::nhwc_used_threads(C / V, rows, 262144);
+    hipLaunchKernelGGL((dla::bn_stats_nhwc_kernel<dev_t, V>),
+                       dim3((int)((used + 255) / 256)), dim3(256),
+                       2 * C * sizeof(float), dla::stream(),
+                       (const dev_t*)x.data_ptr(), sums.data_ptr<float>(), C,
+                       rows, used);
+    fin = dla::bn_finalize_launch(sums, weight, bias, running_mean,
+                                  running_var, C, rows, momentum, eps);
+    hipLaunchKernelGGL((dla::bn_relu_maxpool_fwd_nhwc_kernel<dev_t, V>),
+                       dim3(N * runs), dim3(256), 0, dla::stream(),
+                       (const dev_t*)x.data_ptr(), fin.scale.data_ptr<float>(),
+                       fin.shift.data_ptr<float>(), (dev_t*)pooled.data_ptr(),
+                       slots.data_ptr<uint8_t>(), C, H, W, OH, OW, runs);
+  });
+  HIP_CHECK_ERR();
+  return {pooled, slots, fin.mean, fin.rstd, fin.scale, fin.shift};
+}
+
+// Returns {dx, dweight, dbias} as batchnorm_bwd does.
+std::vector<torch::Tensor> bn_relu_maxpool_bwd(
+    torch::Tensor dpool, torch::Tensor x, torch::Tensor slots,
+    torch::Tensor weight, torch::Tensor mean, torch::Tensor rstd,
+    torch::Tensor scale, torch::Tensor shift) {
+  dla::stem_check(x, "bn_relu_maxpool_bwd");
+  const int N = (int)x.size(0), C = (int)x.size(1);
+  const int H = (int)x.size(2), W = (int)x.size(3);
+  const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
+  const int64_t rows = (int64_t)N * H * W;
+  DLA_CHECK_CUDA(dpool);
+  if (!dla::is_nhwc_rows(dpool))
+    dpool = dpool.contiguous(at::MemoryFormat::ChannelsLast);
+  const std::vector<int64_t> pshape{N, C, OH, OW};
+  TORCH_CHECK(dpool.scalar_type() == x.scalar_type() &&
+                  dpool.sizes() == at::IntArrayRef(pshape),
+              "bn_relu_maxpool_bwd: dpool must be [N, C, OH, OW] of x's dtype");
+  TORCH_CHECK(slots.is_cuda() && slots.scalar_type() == torch::kByte &&
+                  slots.sizes() == at::IntArrayRef(pshape) &&
+                  dla::is_nhwc_rows(slots),
+              "bn_relu_maxpool_bwd: slots must be channels_last uint8 "
+              "[N, C, OH, OW]");
+  for (const auto* t : {&mean, &rstd, &scale, &shift})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kFloat &&
+                    t->is_contiguous() && t->numel() == C,
+                "bn_relu_maxpool_bwd: per-channel tensors must be contiguous "
+                "fp32 [C]");
+  TORCH_CHECK(weight.numel() == C, "bn_relu_maxpool_bwd: weight must be [C]");
+  auto sums = torch::zeros({2 * C}, x.options().dtype(torch::kFloat));
+  auto dx = torch::empty_like(x);
+  auto w32 = weight.to(torch::kFloat).contiguous();
+  DLA_DISPATCH_FLOAT_TYPES(x.scalar_type(), "bn_relu_maxpool_bwd", [&] {
+    constexpr int V = 16 / (int)sizeof(dev_t);
+    const int lanes = C / V;
+    const int64_t used_s = dla::nhwc_used_threads(lanes, rows, 262144);
+    hipLaunchKernelGGL((dla::bn_relu_maxpool_bwd_stats_nhwc_kernel<dev_t, V>),
+                       dim3((int)((used_s + 255) / 256)), dim3(256),
+                       2 * C * sizeof(float), dla::stream(),
+                       (const dev_t*)dpool.data_ptr(),
+                       slots.data_ptr<uint8_t>(), (const dev_t*)x.data_ptr(),
+                       scale.data_ptr<float>(), shift.data_ptr<float>(),
+                       mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                       sums.data_ptr<float>(), C, H, W, OH, OW, rows, used_s);
+    const int64_t used = dla::nhwc_used_threads(lanes, rows, 524288);
+    hipLaunchKernelGGL((dla::bn_relu_maxpool_bwd_dx_nhwc_kernel<dev_t, V>),
+                       dim3((int)((used + 255) / 256)), dim3(256), 0,
+                       dla::stream(), (const dev_t*)dpool.data_ptr(),
+                       slots.data_ptr<uint8_t>(), (const dev_t*)x.data_ptr(),
+                       scale.data_ptr<float>(), shift.data_ptr<float>(),
+                       mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                       w32.data_ptr<float>(), sums.data_ptr<float>(),
+                       (dev_t*)dx.data_ptr(), C, H, W, OH, OW, rows, used,
+                       1.f / (float)rows);
+  });
+  HIP_CHECK_ERR();
+  return {dx, dla::bn_param_grad(sums, C, C, weight),
+          dla::bn_param_grad(sums, 0, C, weight)};
 }

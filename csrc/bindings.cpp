@@ -26,6 +26,20 @@ std::vector<torch::Tensor> batchnorm_bwd(torch::Tensor dy, torch::Tensor x,
                                          c10::optional<torch::Tensor> y,
                                          torch::Tensor weight, torch::Tensor mean,
                                          torch::Tensor rstd, bool relu);
+bool bn_relu_mask_from_x(torch::Tensor x);
+std::vector<torch::Tensor> batchnorm_bwd_ex(
+    torch::Tensor dy, torch::Tensor x, c10::optional<torch::Tensor> y,
+    torch::Tensor weight, torch::Tensor mean, torch::Tensor rstd,
+    c10::optional<torch::Tensor> scale, c10::optional<torch::Tensor> shift,
+    bool relu);
+std::vector<torch::Tensor> bn_relu_maxpool_fwd(
+    torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
+    c10::optional<torch::Tensor> running_mean,
+    c10::optional<torch::Tensor> running_var, double momentum, double eps);
+std::vector<torch::Tensor> bn_relu_maxpool_bwd(
+    torch::Tensor dpool, torch::Tensor x, torch::Tensor slots,
+    torch::Tensor weight, torch::Tensor mean, torch::Tensor rstd,
+    torch::Tensor scale, torch::Tensor shift);
 std::vector<torch::Tensor> batchnorm_fwd_from_sums(
     torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
     torch::Tensor sums, c10::optional<torch::Tensor> running_mean,
@@ -142,6 +156,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("batchnorm_fwd_from_sums", &batchnorm_fwd_from_sums);
   m.def("bn_apply", &bn_apply);
   m.def("batchnorm_bwd", &batchnorm_bwd);
+  m.def("batchnorm_bwd_ex", &batchnorm_bwd_ex);
+  m.def("bn_relu_mask_from_x", &bn_relu_mask_from_x);
+  m.def("bn_relu_maxpool_fwd", &bn_relu_maxpool_fwd);
+  m.def("bn_relu_maxpool_bwd", &bn_relu_maxpool_bwd);
   m.def("bn_add_relu_fwd_from_sums", &bn_add_relu_fwd_from_sums);
   m.def("bn_add_relu_dual_fwd_from_sums", &bn_add_relu_dual_fwd_from_sums);
   m.def("bn_add_relu_bwd", &bn_add_relu_bwd);

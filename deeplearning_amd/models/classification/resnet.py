@@ -9,14 +9,21 @@ epilogue (csrc/conv1x1.hip); 3x3 convs run MIOpen by default with a fully
 hand-written TAPS=9 route available (DLA_CONV3X3=1, see ROADMAP); each
 Bottleneck join is one kernel that applies bn3 (and the downsample bn), adds
 the identity and applies ReLU (DLA_NO_FUSED_JOIN=1 restores bn apply +
-add_relu); BasicBlock joins are one fused add+relu kernel.
+add_relu); BasicBlock joins are one fused add+relu kernel. In train mode the
+stem's bn1 + ReLU + 3x3/s2 max-pool is one apply+pool kernel that never writes
+the BN output and keeps a uint8 window slot in place of int64 indices, with a
+two-pass gather backward (DLA_NO_FUSED_STEM=1 restores bn1 then nn.MaxPool2d);
+eval mode and the other models' stems keep the unfused modules. The ReLU mask
+of every BatchNorm2d(relu=True) backward is recomputed from the raw conv
+output rather than read from the stored BN output (DLA_BN_MASK_FROM_Y=1
+restores the read).
 """
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
 
-from ...ops import BatchNorm2d, add_relu
+from ...ops import BatchNorm2d, add_relu, bn_relu_maxpool
 from ...ops.conv1x1 import (can_pass_input, conv1x1_bn, conv_bn,
                             conv_bn_add_relu)
 from ..registry import register_model
@@ -181,7 +188,9 @@ class ResNet(nn.Module):
         return nn.Sequential(*layers)
 
     def forward_features(self, x):
-        x = self.maxpool(self.bn1(self.conv1(x)))
+        # bn1 + relu + maxpool: one fused apply+pool kernel in train mode when
+        # the route applies, else the two modules as they are
+        x = bn_relu_maxpool(self.conv1(x), self.bn1, self.maxpool)
         x = self.layer1(x)
         x = self.layer2(x)
         x = self.layer3(x)

@@ -11,6 +11,7 @@ from .layernorm import LayerNorm, LayerNorm2d, layer_norm
 from .losses import (CrossEntropyLoss, cross_entropy, sigmoid_focal_loss,
                      soft_target_cross_entropy)
 from .roi_align import MultiScaleRoIAlign, roi_align
+from .stem import bn_relu_maxpool, can_fuse_stem
 from .window import (roll_and_window_partition, window_merge_and_roll,
                      window_partition_eager, window_reverse_eager)
 
@@ -19,6 +20,7 @@ __all__ = [
     "gelu", "silu", "add_relu", "GELU", "SiLU",
     "BatchNorm2d", "FrozenBatchNorm2d",
     "conv_bn", "conv1x1_bn", "conv_bn_add_relu",
+    "bn_relu_maxpool", "can_fuse_stem",
     "box_iou", "generalized_box_iou", "bbox_iou_aligned", "box_area", "nms",
     "batched_nms", "clip_boxes_to_image", "remove_small_boxes",
     "DropPath", "drop_path", "ModelEMA",

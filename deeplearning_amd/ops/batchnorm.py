@@ -6,6 +6,8 @@ Reference parity: nn.BatchNorm2d everywhere; FrozenBatchNorm2d
 """
 from __future__ import annotations
 
+import os
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -13,21 +15,50 @@ import torch.nn.functional as F
 from ._ext import dense, ext, use_hip
 
 
+def _mask_from_y() -> bool:
+    return os.environ.get("DLA_BN_MASK_FROM_Y", "0") == "1"  # A/B runs
+
+
+def save_bn_for_backward(ctx, x, y, weight, mean, rstd, scale, shift, relu):
+    """Save what batchnorm_bwd_ex needs. The ReLU mask comes from x through
+    the forward's own scale/shift where the extension's rule allows it
+    (channels_last), so y is not saved there; otherwise, or with
+    DLA_BN_MASK_FROM_Y=1, from the stored y as before."""
+    ctx.relu = relu
+    ctx.mask_from_x = bool(relu and not _mask_from_y() and
+                           ext().bn_relu_mask_from_x(x))
+    if ctx.mask_from_x:
+        ctx.save_for_backward(x, weight, mean, rstd, scale, shift)
+    elif relu:
+        ctx.save_for_backward(x, weight, mean, rstd, y)
+    else:
+        ctx.save_for_backward(x, weight, mean, rstd)
+
+
+def bn_backward(ctx, dy):
+    """(dx, dweight, dbias) from what save_bn_for_backward kept."""
+    x, weight, mean, rstd, *rest = ctx.saved_tensors
+    y = scale = shift = None
+    if ctx.mask_from_x:
+        scale, shift = rest
+    elif ctx.relu:
+        y, = rest
+    return ext().batchnorm_bwd_ex(dy, x, y, weight, mean, rstd, scale, shift,
+                                  ctx.relu)
+
+
 class _BNFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, relu):
         x = dense(x)
-        y, mean, rstd = ext().batchnorm_fwd(
+        y, mean, rstd, scale, shift = ext().batchnorm_fwd(
             x, weight, bias, running_mean, running_var, momentum, eps, relu)
-        ctx.save_for_backward(x, y, weight, mean, rstd)
-        ctx.relu = relu
+        save_bn_for_backward(ctx, x, y, weight, mean, rstd, scale, shift, relu)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, y, weight, mean, rstd = ctx.saved_tensors
-        dx, dw, db = ext().batchnorm_bwd(
-            dy, x, y if ctx.relu else None, weight, mean, rstd, ctx.relu)
+        dx, dw, db = bn_backward(ctx, dy)
         return dx, dw, db, None, None, None, None, None
 
 

@@ -20,6 +20,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from ._ext import ext, use_hip
+from .batchnorm import bn_backward, save_bn_for_backward
 
 
 def _flatten_nhwc(x: torch.Tensor) -> torch.Tensor:
@@ -112,18 +113,16 @@ class _BNFromStatsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, sums, running_mean, running_var,
                 momentum, eps, relu):
-        y, mean, rstd = ext().batchnorm_fwd_from_sums(
+        y, mean, rstd, scale, shift = ext().batchnorm_fwd_from_sums(
             x, weight, bias, sums, running_mean, running_var, momentum, eps,
             relu)
-        ctx.save_for_backward(x, y, weight, mean, rstd)
-        ctx.relu = relu
+        save_bn_for_backward(ctx, x, y, weight, mean, rstd, scale, shift,
+                             relu)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, y, weight, mean, rstd = ctx.saved_tensors
-        dx, dw, db = ext().batchnorm_bwd(
-            dy, x, y if ctx.relu else None, weight, mean, rstd, ctx.relu)
+        dx, dw, db = bn_backward(ctx, dy)
         return dx, dw, db, None, None, None, None, None, None
 
 
