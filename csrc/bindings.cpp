@@ -83,6 +83,14 @@ std::vector<torch::Tensor> conv3x3_fwd(torch::Tensor a, torch::Tensor w9,
                                        bool relu, bool want_stats);
 torch::Tensor conv3x3_wgrad(torch::Tensor dy, torch::Tensor x, int64_t imgH,
                             int64_t imgW);
+// dwconv.hip
+torch::Tensor dwconv_fwd(torch::Tensor x, torch::Tensor weight,
+                         c10::optional<torch::Tensor> bias, int64_t stride);
+torch::Tensor dwconv_dgrad(torch::Tensor dy, torch::Tensor weight, int64_t H,
+                           int64_t W, int64_t stride);
+std::vector<torch::Tensor> dwconv_wgrad(torch::Tensor dy, torch::Tensor x,
+                                        int64_t K, int64_t stride,
+                                        bool out_f32);
 // reorder.hip
 torch::Tensor transpose2d(torch::Tensor src);
 torch::Tensor stride2_gather(torch::Tensor x);
@@ -175,6 +183,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("residual") = py::none(), py::arg("relu") = false,
         py::arg("want_stats") = false);
   m.def("conv3x3_wgrad", &conv3x3_wgrad);
+  m.def("dwconv_fwd", &dwconv_fwd, py::arg("x"), py::arg("weight"),
+        py::arg("bias") = py::none(), py::arg("stride") = 1);
+  m.def("dwconv_dgrad", &dwconv_dgrad);
+  m.def("dwconv_wgrad", &dwconv_wgrad);
   m.def("transpose2d", &transpose2d);
   m.def("stride2_gather", &stride2_gather);
   m.def("stride2_scatter", &stride2_scatter);

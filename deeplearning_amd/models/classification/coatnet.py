@@ -9,7 +9,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from ...ops import GELU, BatchNorm2d, LayerNorm
+from ...ops import GELU, BatchNorm2d, DepthwiseConv2d, LayerNorm
 from ..registry import register_model
 from .vit import Mlp
 
@@ -22,7 +22,7 @@ class MBConvBlock(nn.Module):
         self.pre_norm = BatchNorm2d(cin)
         self.conv = nn.Sequential(
             nn.Conv2d(cin, mid, 1, bias=False), BatchNorm2d(mid, relu=True),
-            nn.Conv2d(mid, mid, 3, stride, 1, groups=mid, bias=False),
+            DepthwiseConv2d(mid, mid, 3, stride, 1, groups=mid, bias=False),
             BatchNorm2d(mid, relu=True),
             nn.Conv2d(mid, cout, 1, bias=False), BatchNorm2d(cout))
         self.proj = None

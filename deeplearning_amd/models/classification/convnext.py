@@ -9,7 +9,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from ...ops import DropPath, LayerNorm, LayerNorm2d, gelu
+from ...ops import DepthwiseConv2d, DropPath, LayerNorm, LayerNorm2d, gelu
 from ..registry import register_model
 
 
@@ -18,7 +18,7 @@ class ConvNeXtBlock(nn.Module):
 
     def __init__(self, dim, drop_path=0.0, layer_scale_init=1e-6):
         super().__init__()
-        self.dwconv = nn.Conv2d(dim, dim, 7, padding=3, groups=dim)
+        self.dwconv = DepthwiseConv2d(dim, dim, 7, padding=3, groups=dim)
         self.norm = LayerNorm(dim, eps=1e-6)
         self.pwconv1 = nn.Linear(dim, 4 * dim)
         self.pwconv2 = nn.Linear(4 * dim, dim)

@@ -12,7 +12,7 @@ from functools import partial
 import torch
 import torch.nn as nn
 
-from ...ops import BatchNorm2d, DropPath, SiLU
+from ...ops import BatchNorm2d, DepthwiseConv2d, DropPath, SiLU
 from ..registry import register_model
 
 
@@ -26,8 +26,9 @@ def _round_channels(c, width_mult, divisor=8):
 
 class ConvBNAct(nn.Sequential):
     def __init__(self, cin, cout, k=3, stride=1, groups=1, act=True):
-        layers = [nn.Conv2d(cin, cout, k, stride, (k - 1) // 2, groups=groups,
-                            bias=False),
+        conv = DepthwiseConv2d if groups == cin == cout else nn.Conv2d
+        layers = [conv(cin, cout, k, stride, (k - 1) // 2, groups=groups,
+                       bias=False),
                   BatchNorm2d(cout, eps=1e-3, momentum=0.1)]
         if act:
             layers.append(SiLU())

@@ -10,7 +10,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from ...ops import BatchNorm2d
+from ...ops import BatchNorm2d, DepthwiseConv2d
 from ..registry import register_model
 
 
@@ -34,7 +34,7 @@ class ShuffleUnitV1(nn.Module):
             BatchNorm2d(mid, relu=True))
         self.groups = groups
         self.dwconv = nn.Sequential(
-            nn.Conv2d(mid, mid, 3, stride, 1, groups=mid, bias=False),
+            DepthwiseConv2d(mid, mid, 3, stride, 1, groups=mid, bias=False),
             BatchNorm2d(mid))
         self.gconv2 = nn.Sequential(
             nn.Conv2d(mid, cout, 1, groups=groups, bias=False),
@@ -87,7 +87,8 @@ class InvertedResidualV2(nn.Module):
         branch_c = cout // 2
         if stride > 1:
             self.branch1 = nn.Sequential(
-                nn.Conv2d(cin, cin, 3, stride, 1, groups=cin, bias=False),
+                DepthwiseConv2d(cin, cin, 3, stride, 1, groups=cin,
+                                bias=False),
                 BatchNorm2d(cin),
                 nn.Conv2d(cin, branch_c, 1, bias=False),
                 BatchNorm2d(branch_c, relu=True))
@@ -97,8 +98,8 @@ class InvertedResidualV2(nn.Module):
         self.branch2 = nn.Sequential(
             nn.Conv2d(in2, branch_c, 1, bias=False),
             BatchNorm2d(branch_c, relu=True),
-            nn.Conv2d(branch_c, branch_c, 3, stride, 1, groups=branch_c,
-                      bias=False),
+            DepthwiseConv2d(branch_c, branch_c, 3, stride, 1,
+                            groups=branch_c, bias=False),
             BatchNorm2d(branch_c),
             nn.Conv2d(branch_c, branch_c, 1, bias=False),
             BatchNorm2d(branch_c, relu=True))

@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ...ops import BatchNorm2d
+from ...ops import BatchNorm2d, DepthwiseConv2d
 from ..registry import register_model
 
 
@@ -29,8 +29,8 @@ def conv_bn(cin, cout, k, stride=1, padding=0, relu=True, groups=1):
 class SeparableConv2d(nn.Module):
     def __init__(self, cin, cout, k=3, stride=1, padding=1):
         super().__init__()
-        self.depthwise = nn.Conv2d(cin, cin, k, stride, padding, groups=cin,
-                                   bias=False)
+        self.depthwise = DepthwiseConv2d(cin, cin, k, stride, padding,
+                                         groups=cin, bias=False)
         self.pointwise = nn.Conv2d(cin, cout, 1, bias=False)
 
     def forward(self, x):

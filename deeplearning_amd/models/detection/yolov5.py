@@ -14,7 +14,7 @@ import math
 import torch
 import torch.nn as nn
 
-from ...ops import BatchNorm2d, SiLU, bbox_iou_aligned
+from ...ops import BatchNorm2d, DepthwiseConv2d, SiLU, bbox_iou_aligned
 from ..registry import register_model
 
 
@@ -25,7 +25,8 @@ def autopad(k, p=None):
 class Conv(nn.Module):
     def __init__(self, c1, c2, k=1, s=1, p=None, g=1, act=True):
         super().__init__()
-        self.conv = nn.Conv2d(c1, c2, k, s, autopad(k, p), groups=g, bias=False)
+        conv = DepthwiseConv2d if g == c1 == c2 else nn.Conv2d
+        self.conv = conv(c1, c2, k, s, autopad(k, p), groups=g, bias=False)
         self.bn = BatchNorm2d(c2)
         self.act = SiLU() if act else nn.Identity()
 

@@ -6,6 +6,7 @@ from .boxes import (batched_nms, bbox_iou_aligned, box_area, box_iou,
                     clip_boxes_to_image, generalized_box_iou, nms,
                     remove_small_boxes)
 from .drop import DropPath, drop_path
+from .dwconv import DepthwiseConv2d, can_use_dwconv, depthwise_conv2d
 from .ema import ModelEMA
 from .layernorm import LayerNorm, LayerNorm2d, layer_norm
 from .losses import (CrossEntropyLoss, cross_entropy, sigmoid_focal_loss,
@@ -21,6 +22,7 @@ __all__ = [
     "BatchNorm2d", "FrozenBatchNorm2d",
     "conv_bn", "conv1x1_bn", "conv_bn_add_relu",
     "bn_relu_maxpool", "can_fuse_stem",
+    "depthwise_conv2d", "can_use_dwconv", "DepthwiseConv2d",
     "box_iou", "generalized_box_iou", "bbox_iou_aligned", "box_area", "nms",
     "batched_nms", "clip_boxes_to_image", "remove_small_boxes",
     "DropPath", "drop_path", "ModelEMA",
