@@ -19,9 +19,11 @@
 //  - epilogue stores go through an LDS f32 transpose so global writes are
 //    row-major 8B/lane coalesced (fragment layout is column-per-lane)
 //
-// wgrad: dW[N][K] = sum_m dy[m][n] * x[m][k] — separate kernel contracting
-// over M with transposed LDS images (scatter ds_write staging, m-contiguous
-// fragment reads), fp32 atomicAdd accumulation over M-split blocks.
+// wgrad: dW[N][K] = sum_m dy[m][n] * x[m][k] — separate kernels contracting
+// over M. 1x1: conv1x1_wgrad2_kernel (row-major glds staging, transposed
+// ds_read_b64_tr_b16 fragment reads, per-split slab + fixed-order finalize).
+// 3x3 and the DLA_C1X1_WGRAD_V1=1 A/B route: conv1x1_wgrad_kernel (scatter
+// ds_write staging into transposed images, fp32 atomicAdd over M-splits).
 #include <cstdlib>
 
 #include "common.h"
@@ -506,6 +508,217 @@ __global__ __launch_bounds__((BCO * BCI >= 8192) ? 512 : 256) void conv1x1_wgrad
         }
 }
 
+// ---------------------------------------------------------------------------
+// wgrad v2 (1x1 only): dW[N][K] = sum_m dy[m][n] * x[m][k], no atomics.
+//  - both operands are staged exactly as they lie in memory, as row-major
+//    [KM m][BC ch] LDS images, 16 B per lane straight from global
+//    (glds16), double-buffered with one barrier per 64-row step
+//  - the transpose happens in the fragment read: two ds_read_b64_tr_b16 per
+//    16ch x 32m operand fragment (guide T10). Group g of 16 lanes reads rows
+//    8g..8g+3 then 8g+4..8g+7 of the k-step, so lane (g, i) ends up with
+//    channel i, m = 8g + j in element j: the MFMA's natural k order, for
+//    both operands alike
+//  - a 32-lane half touches 8 rows (q = 0..3 of two blocks 8 rows apart),
+//    32 B each; wg_swz XORs the 16-byte chunk index so they fall on 8
+//    different bank octets (bank = (byte/4) % 64). The XOR never touches
+//    chunk bit 0, so the 32 bytes of one block row stay contiguous. It is
+//    applied to the glds SOURCE address (linear LDS destination) and again
+//    on the fragment read
+//  - the last, partial step of a chunk stages through registers with zero
+//    fill into the same image; rows at or past m_end are never read
+//  - splits > 1: each split stores its fp32 tile into out[split][N][K] and
+//    wgrad_finalize_kernel sums the splits in fixed order; splits == 1
+//    stores dW directly
+//  - the 1-D grid is remapped so the tiles of one m-chunk run on one XCD
+//    (ids congruent mod 8 share an XCD) and share the chunk through its L2;
+//    only speed depends on that placement
+// ---------------------------------------------------------------------------
+using bf16x4 = __attribute__((ext_vector_type(4))) short;
+
+template <int BC>
+__device__ __forceinline__ int wg_swz(int row) {
+  static_assert(BC == 64 || BC == 128, "128 B or 256 B rows");
+  // 128 B rows: odd rows already sit in the other half of the 256 B bank row
+  if (BC == 64) return (((row >> 1) & 1) << 2) | (((row >> 3) & 1) << 1);
+  return ((row & 3) << 2) | (((row >> 3) & 1) << 1);
+}
+
+template <int BCO, int BCI>
+__global__ __launch_bounds__(256) void conv1x1_wgrad2_kernel(
+    const bf16* __restrict__ dy,  // [M,N]
+    const bf16* __restrict__ x,   // [M,K]
+    float* __restrict__ out,      // [splits][N][K] (dW itself at splits == 1)
+    int64_t M, int K, int N, int64_t chunk, int tiles, int total) {
+  constexpr int KM = 64;  // m rows per step
+  constexpr int WGC = 2, WGI = 2;  // 4 waves, 2 over co x 2 over ci
+  constexpr int WCO = BCO / WGC, WCI = BCI / WGI;
+  constexpr int FCO = WCO / 16, FCI = WCI / 16;
+  constexpr int IMG = KM * (BCO + BCI) * 2;  // bytes of one buffer
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+
+  // XCD-aware id remap: XCD i runs logical ids [i*per, (i+1)*per)
+  const int per = (int)gridDim.x >> 3;
+  const int logical = ((int)blockIdx.x & 7) * per + ((int)blockIdx.x >> 3);
+  if (logical >= total) return;
+  const int split = logical / tiles;
+  const int tile = logical - split * tiles;
+  const int n0 = (tile % (N / BCO)) * BCO;
+  const int k0 = (tile / (N / BCO)) * BCI;
+  const int64_t m_begin = (int64_t)split * chunk;
+  const int64_t m_end = m_begin + chunk < M ? m_begin + chunk : M;
+  const int nfull = (int)((m_end - m_begin) / KM);
+  const int nsteps = (int)((m_end - m_begin + KM - 1) / KM);
+
+  extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+  auto dy_img = [&](int buf) { return lds_raw + buf * IMG; };
+  auto x_img = [&](int buf) { return lds_raw + buf * IMG + KM * BCO * 2; };
+
+  // stage rows [mt, mt+KM) of g[:, ch0 : ch0+BC] into a [KM][BC] image
+  auto stage_op = [&](char* img, const bf16* g, int stride, int ch0,
+                      int64_t mt, bool full, auto bc_tag) {
+    constexpr int BC = decltype(bc_tag)::value;
+    constexpr int LPR = BC / 8;    // 16 B chunks (lanes) per row
+    constexpr int RPP = 64 / LPR;  // rows per 1 KB piece
+    const char* base = (const char*)(g + mt * (int64_t)stride + ch0);
+    if (full) {
+#pragma unroll
+      for (int pp = 0; pp < (KM / RPP) / 4; ++pp) {
+        const int p = wave + pp * 4;
+        const int row = p * RPP + lane / LPR;
+        const int ch = (lane % LPR) ^ wg_swz<BC>(row);
+        glds16((const bf16*)(base + (int64_t)row * stride * 2 + ch * 16),
+               (bf16*)(img + p * 1024));
+      }
+    } else {
+#pragma unroll
+      for (int it = 0; it < (KM * LPR) / 256; ++it) {
+        const int idx = (int)threadIdx.x + it * 256;
+        const int row = idx / LPR;
+        const int ch = (idx % LPR) ^ wg_swz<BC>(row);
+        Vec<bf16, 8> v;
+        if (mt + row < m_end) {
+          v = vload<bf16, 8>(
+              (const bf16*)(base + (int64_t)row * stride * 2 + ch * 16));
+        } else {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) v.v[j] = from_f32<bf16>(0.f);
+        }
+        vstore<bf16, 8>((bf16*)(img + idx * 16), v);
+      }
+    }
+  };
+  auto stage = [&](int buf, int s) {
+    const int64_t mt = m_begin + (int64_t)s * KM;
+    const bool full = s < nfull;  // block-uniform
+    stage_op(dy_img(buf), dy, N, n0, mt, full,
+             std::integral_constant<int, BCO>{});
+    stage_op(x_img(buf), x, K, k0, mt, full,
+             std::integral_constant<int, BCI>{});
+  };
+
+  // per-lane fragment read offsets: lane 4q+p of group g supplies the
+  // address of row 8g+q (+32ks +4h as an immediate), columns 4p..4p+3 of the
+  // fragment's 16 channels. wg_swz depends only on (q, g) for those rows.
+  const int fg = lane >> 4, fq = (lane >> 2) & 3, fp = lane & 3;
+  const int frow = 8 * fg + fq;
+  int offa[FCO], offb[FCI];
+#pragma unroll
+  for (int mi = 0; mi < FCO; ++mi) {
+    const int chunk16 = ((wave / WGI) * WCO + mi * 16) / 8 + (fp >> 1);
+    offa[mi] = frow * (BCO * 2) + ((chunk16 ^ wg_swz<BCO>(frow)) << 4) +
+               8 * (fp & 1);
+  }
+#pragma unroll
+  for (int ni = 0; ni < FCI; ++ni) {
+    const int chunk16 = ((wave % WGI) * WCI + ni * 16) / 8 + (fp >> 1);
+    offb[ni] = frow * (BCI * 2) + ((chunk16 ^ wg_swz<BCI>(frow)) << 4) +
+               8 * (fp & 1);
+  }
+  auto tr_frag = [&](const char* p, int rowb) {
+    using lds_v4 = __attribute__((address_space(3))) bf16x4;
+    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)p);
+    const bf16x4 hi =
+        __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(p + 4 * rowb));
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+  };
+
+  f32x4 acc[FCO][FCI];
+#pragma unroll
+  for (int mi = 0; mi < FCO; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < FCI; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  stage(0, 0);
+  for (int s = 0; s < nsteps; ++s) {
+    // step s has landed (vmcnt(0) in the barrier) and every wave is done
+    // reading the other buffer
+    __syncthreads();
+    if (s + 1 < nsteps) stage((s + 1) & 1, s + 1);
+    const char* da = dy_img(s & 1);
+    const char* xa = x_img(s & 1);
+#pragma unroll
+    for (int ks = 0; ks < KM / 32; ++ks) {
+      bf16x8 af[FCO], bfr[FCI];
+#pragma unroll
+      for (int mi = 0; mi < FCO; ++mi)
+        af[mi] = tr_frag(da + ks * 32 * (BCO * 2) + offa[mi], BCO * 2);
+#pragma unroll
+      for (int ni = 0; ni < FCI; ++ni)
+        bfr[ni] = tr_frag(xa + ks * 32 * (BCI * 2) + offb[ni], BCI * 2);
+#pragma unroll
+      for (int mi = 0; mi < FCO; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < FCI; ++ni)
+          acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              af[mi], bfr[ni], acc[mi][ni], 0, 0, 0);
+    }
+  }
+
+  float* o = out + (int64_t)split * N * K;
+  const int wco = (wave / WGI) * WCO, wci = (wave % WGI) * WCI;
+#pragma unroll
+  for (int mi = 0; mi < FCO; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < FCI; ++ni)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int co = n0 + wco + mi * 16 + (lane >> 4) * 4 + r;
+        const int ci = k0 + wci + ni * 16 + (lane & 15);
+        o[(int64_t)co * K + ci] = acc[mi][ni][r];
+      }
+}
+
+// dW = sum over splits of slab[split], in an order fixed by (splits, G):
+// thread (g, o) sums the splits [g*per, (g+1)*per) of float4 output o in
+// ascending order, then the G group sums are added in ascending g. G > 1
+// gives a small weight with many splits enough threads to pull the slab.
+// G is a power of two <= 64; n4 = N*K/4 is a multiple of 256.
+__global__ __launch_bounds__(256) void wgrad_finalize_kernel(
+    const float* __restrict__ slab, float* __restrict__ dW, int n4,
+    int splits, int G, int per) {
+  __shared__ f32x4 part[256];
+  const int outs = 256 / G;  // float4 outputs per block
+  const int g = threadIdx.x / outs, o = threadIdx.x % outs;
+  const int i = blockIdx.x * outs + o;
+  const f32x4* p = (const f32x4*)slab + i;
+  const int z0 = g * per;
+  const int z1 = z0 + per < splits ? z0 + per : splits;
+  f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+  for (int z = z0; z < z1; ++z) s += p[(int64_t)z * n4];
+  if (G == 1) {  // block-uniform
+    ((f32x4*)dW)[i] = s;
+    return;
+  }
+  part[threadIdx.x] = s;
+  __syncthreads();
+  if (g == 0) {
+    for (int j = 1; j < G; ++j) s += part[j * outs + o];
+    ((f32x4*)dW)[i] = s;
+  }
+}
+
 }  // namespace dla
 
 // A [M,K] bf16, B [N,K] bf16 -> C = A @ B^T [M,N] bf16, with fused epilogue.
@@ -679,6 +892,70 @@ std::vector<torch::Tensor> conv3x3_fwd(torch::Tensor a, torch::Tensor w9,
   return {C, sums};
 }
 
+// wgrad v2 launcher: tile choice, M-split count, slab + finalize.
+static torch::Tensor conv1x1_wgrad_v2(const torch::Tensor& dy,
+                                      const torch::Tensor& x, int64_t M,
+                                      int K, int N) {
+  auto opts_f = x.options().dtype(torch::kFloat);
+  if (M == 0) return torch::zeros({N, K}, opts_f);
+  auto dW = torch::empty({N, K}, opts_f);
+  auto launch = [&](auto cotag, auto citag) {
+    constexpr int BCO = decltype(cotag)::value;
+    constexpr int BCI = decltype(citag)::value;
+    constexpr int lds = 2 * 64 * (BCO + BCI) * 2;
+    constexpr int bpc = std::min(4, 163840 / lds);  // resident blocks per CU
+    const int tiles = (N / BCO) * (K / BCI);
+    // enough splits for one resident wave of blocks on 256 CUs, but chunks
+    // of at least 4 steps, and slab traffic (write + read, 8 B per output
+    // and split) no more than the operand bytes 2*M*(N+K)
+    int64_t s = std::max<int64_t>(1, (256 * bpc) / tiles);
+    s = std::min<int64_t>(s, std::max<int64_t>(1, M / 256));
+    s = std::min<int64_t>(
+        s, std::max<int64_t>(1, M * (N + K) / (4 * (int64_t)N * K)));
+    const int64_t chunk = (((M + s - 1) / s + 63) / 64) * 64;
+    const int splits = (int)((M + chunk - 1) / chunk);
+    const int total = tiles * splits;
+    torch::Tensor slab;
+    float* out = dW.data_ptr<float>();
+    if (splits > 1) {
+      slab = torch::empty({splits, N, K}, opts_f);
+      out = slab.data_ptr<float>();
+    }
+    static_assert(lds <= 65536, "needs hipFuncSetAttribute above 64 KB");
+    hipLaunchKernelGGL((dla::conv1x1_wgrad2_kernel<BCO, BCI>),
+                       dim3(((total + 7) / 8) * 8), dim3(256), lds,
+                       dla::stream(), (const dla::bf16*)dy.data_ptr(),
+                       (const dla::bf16*)x.data_ptr(), out, M, K, N, chunk,
+                       tiles, total);
+    if (splits > 1) {
+      const int n4 = N * K / 4;
+      // split groups per output: enough for ~64 K threads to pull the slab,
+      // while each group still sums at least 4 splits
+      int G = 1;
+      while (G < 64 && n4 * G < 65536 && splits >= 8 * G) G *= 2;
+      hipLaunchKernelGGL(dla::wgrad_finalize_kernel, dim3(n4 / (256 / G)),
+                         dim3(256), 0, dla::stream(), (const float*)out,
+                         dW.data_ptr<float>(), n4, splits, G,
+                         (splits + G - 1) / G);
+    }
+  };
+  using std::integral_constant;
+  const bool n128 = N % 128 == 0, k128 = K % 128 == 0;
+  // 128x128 measured best wherever it divides; a whole-weight 256x64 /
+  // 64x256 tile and 64x128 / 128x64 at the fat weights were no faster
+  // (profiles/wgrad_v2_ab.txt)
+  if (n128 && k128)
+    launch(integral_constant<int, 128>{}, integral_constant<int, 128>{});
+  else if (k128)
+    launch(integral_constant<int, 64>{}, integral_constant<int, 128>{});
+  else if (n128)
+    launch(integral_constant<int, 128>{}, integral_constant<int, 64>{});
+  else
+    launch(integral_constant<int, 64>{}, integral_constant<int, 64>{});
+  HIP_CHECK_ERR();
+  return dW;
+}
+
 // dW[N,K] fp32 = dy[M,N]^T @ x[M,K]
 torch::Tensor conv1x1_wgrad(torch::Tensor dy, torch::Tensor x) {
   DLA_CHECK_INPUT(dy);
@@ -690,6 +967,9 @@ torch::Tensor conv1x1_wgrad(torch::Tensor dy, torch::Tensor x) {
   const int K = (int)x.size(1), N = (int)dy.size(1);
   TORCH_CHECK(dy.size(0) == M, "conv1x1_wgrad: M mismatch");
   TORCH_CHECK(K % 64 == 0 && N % 64 == 0, "conv1x1_wgrad: K,N must be %64");
+  // DLA_C1X1_WGRAD_V1=1: the scatter-staged, atomicAdd kernel (same-build A/B)
+  const char* v1 = std::getenv("DLA_C1X1_WGRAD_V1");
+  if (v1 == nullptr || v1[0] != '1') return conv1x1_wgrad_v2(dy, x, M, K, N);
   auto dW = torch::zeros({N, K}, x.options().dtype(torch::kFloat));
   auto launch = [&](auto cotag, auto citag) {
     constexpr int BCO = decltype(cotag)::value;

@@ -4,8 +4,11 @@
 vs conv + separate BN, and CE old-vs-new launch overhead.
 
 Run on a GPU box:  python tools/bench_conv1x1.py [--quick]
+                   python tools/bench_conv1x1.py --wgrad-ab   (wgrad only: old
+                   route DLA_C1X1_WGRAD_V1=1 against new, with the byte floor)
 """
 import argparse
+import os
 import sys
 import time
 from pathlib import Path
@@ -40,11 +43,49 @@ SHAPES = [
 ]
 
 
+# best measured unique-byte rate of the forward kernel (802816x256x64 in
+# profiles/conv1x1_bench.txt): the yardstick for the wgrad byte floor
+FLOOR_GBPS = 5144.0
+
+
+def wgrad_ab(B, iters):
+    """wgrad only, old route (DLA_C1X1_WGRAD_V1=1: scatter staging + fp32
+    atomics + zero fill) against the default one in the same process. The
+    switch is read at every call. Unique bytes = 2*M*(N+K): each operand
+    read once; floor = those bytes at FLOOR_GBPS."""
+    print(f"batch={B}  wgrad A/B, {iters} calls per timing, best of 3 "
+          "alternating rounds")
+    print(f"{'shape MxKxN':>24} {'v1 ms':>8} {'v2 ms':>8} {'v1/v2':>6} "
+          f"{'v2 GB/s':>8} {'floor ms':>9} {'v2/floor':>9}")
+    for HW, K, N in SHAPES:
+        M = B * HW
+        x = torch.randn(M, K, device="cuda").to(torch.bfloat16)
+        dy = torch.randn(M, N, device="cuda").to(torch.bfloat16)
+        best = {"1": float("inf"), "0": float("inf")}
+        for _ in range(3):
+            for v in ("1", "0"):
+                os.environ["DLA_C1X1_WGRAD_V1"] = v
+                t = timeit(lambda: ext().conv1x1_wgrad(dy, x), iters)
+                best[v] = min(best[v], t)
+        os.environ.pop("DLA_C1X1_WGRAD_V1")
+        nbytes = 2 * M * (N + K)
+        floor = nbytes / (FLOOR_GBPS * 1e9) * 1e3
+        gbps = nbytes / (best["0"] * 1e-3) / 1e9
+        print(f"{f'{M}x{K}x{N}':>24} {best['1']:8.3f} {best['0']:8.3f} "
+              f"{best['1'] / best['0']:6.2f} {gbps:8.0f} {floor:9.3f} "
+              f"{best['0'] / floor:9.2f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--wgrad-ab", action="store_true",
+                    help="time only wgrad, old route against new")
     args = ap.parse_args()
+    if args.wgrad_ab:
+        wgrad_ab(args.batch, 50 if args.quick else 200)
+        return
     iters = 20 if args.quick else 50
     B = args.batch
     torch.backends.cudnn.benchmark = True
