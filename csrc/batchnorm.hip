@@ -216,8 +216,8 @@ __global__ void bn_bwd_dx_kernel(const dev_t* __restrict__ dy,
 // lanes_per_row)*V, row = t / lanes_per_row), rows strided by
 // used_threads/lanes_per_row. Adjacent lanes read adjacent 16B channel chunks
 // (fully coalesced); per-channel parameters load ONCE per thread (c0 is
-// loop-invariant). Stats kernels block-reduce through LDS (ds_add_f32) and
-// issue 2*C global atomics per block.
+// loop-invariant). That is the mapping of the apply and dx kernels; the
+// per-channel reduction kernels have their own, below.
 
 inline int64_t nhwc_used_threads(int lanes_per_row, int64_t rows,
                                  int64_t target_lanes) {
@@ -227,39 +227,164 @@ inline int64_t nhwc_used_threads(int lanes_per_row, int64_t rows,
   return (int64_t)lanes_per_row * k;
 }
 
-template <typename dev_t, int V>
-__global__ void bn_stats_nhwc_kernel(const dev_t* __restrict__ x,
-                                     float* __restrict__ sums, int C,
-                                     int64_t rows, int64_t used) {
-  extern __shared__ float ls[];  // 2*C floats
-  for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) ls[i] = 0.f;
-  __syncthreads();
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int lanes_per_row = C / V;
-  if (t < used) {
-    const int c0 = (int)(t % lanes_per_row) * V;
-    const int64_t rstride = used / lanes_per_row;
-    float s[V], q[V];
+// ---- NHWC per-channel reductions: no atomics, one slab row per block -------
+// The reduction kernels (stats, backward stats, join backward stats, stem
+// backward stats) run on a grid of (channel chunks, row splits). A block owns
+// `bl` <= kRedLanes adjacent V-wide lanes of the row and rb = 256 / bl
+// row-lanes; thread (rl, lane) sums rows split*rb + rl, + splits*rb, ... in
+// registers. The block then sums its row-lanes per channel in ascending order
+// through LDS and stores the result to row `split` of a [splits, NS*C] slab
+// with plain stores: every slab element is written by exactly one block,
+// whatever (rows, C), because the column ranges of the chunks partition
+// [0, C) and every (chunk, split) block stores its whole range, zeros when it
+// had no rows. A second small kernel (bn_slab_reduce_kernel, or the finalize
+// kernel in forward) sums the slab rows in a fixed order, so every BN result
+// is bit-reproducible.
+constexpr int kRedThreads = 256;
+constexpr int kRedLanes = 32;      // widest channel chunk of a block, in lanes
+constexpr int kRedBlocks = 2048;   // grid target: 8 blocks per CU
+constexpr int kRedMaxParts = 512;  // most slab rows
+constexpr int kRedMinRows = 8;     // stop splitting below 8 rows per thread
+// Rows in flight per thread: about eight 16-byte loads, whatever the number
+// of tensors a kernel reads per row.
+constexpr int red_unroll(int tensors) { return tensors <= 2 ? 4 : 2; }
+
+// Four waves per SIMD is the occupancy these kernels are written for: with a
+// 128-register budget hipcc keeps the unrolled rows' loads together; asked
+// for more waves it sinks every load to its first use to save registers.
+#define DLA_RED_KERNEL \
+  __launch_bounds__(dla::kRedThreads) __attribute__((amdgpu_waves_per_eu(1, 4)))
+
+struct NhwcRedTile {
+  int bl, rb, chunks, parts;
+};
+
+inline NhwcRedTile nhwc_red_tile(int lanes_per_row, int64_t rows,
+                                 int blocks = kRedBlocks,
+                                 int max_parts = kRedMaxParts) {
+  NhwcRedTile t;
+  t.chunks = (lanes_per_row + kRedLanes - 1) / kRedLanes;
+  t.bl = (lanes_per_row + t.chunks - 1) / t.chunks;  // chunks*bl >= lanes
+  t.rb = kRedThreads / t.bl;
+  const int64_t per_part = (int64_t)t.rb * kRedMinRows;
+  const int64_t by_rows = (rows + per_part - 1) / per_part;
+  const int64_t p = std::min<int64_t>(
+      std::min<int64_t>(blocks / t.chunks, max_parts), by_rows);
+  t.parts = (int)std::max<int64_t>(p, 1);
+  return t;
+}
+
+struct NhwcRedPos {
+  int c0;           // first channel of this thread
+  int64_t row;      // first row
+  int64_t rstride;  // row step
+  bool active;      // false: a lane past C or a row-lane past rb
+};
+
+template <int V>
+__device__ __forceinline__ NhwcRedPos nhwc_red_pos(int C, int bl, int rb) {
+  const int lane = threadIdx.x % bl, rl = threadIdx.x / bl;
+  const int gl = blockIdx.x * bl + lane;
+  NhwcRedPos p;
+  p.c0 = gl * V;
+  p.row = (int64_t)blockIdx.y * rb + rl;
+  p.rstride = (int64_t)gridDim.y * rb;
+  p.active = rl < rb && gl < C / V;
+  return p;
+}
+
+// add(r, load(r)) for this thread's rows in ascending order. load(r) returns
+// the row's vectors; U rows are loaded before the first is added, so
+// that their loads are in flight together (hipcc does not hoist them itself).
+template <int U, typename L, typename A>
+__device__ __forceinline__ void nhwc_red_rows(const NhwcRedPos& p,
+                                              int64_t rows, L&& load, A&& add) {
+  if (!p.active) return;
+  using D = decltype(load(int64_t{}));
+  int64_t r = p.row;
+  for (; r + (U - 1) * p.rstride < rows; r += U * p.rstride) {
+    D d[U];
 #pragma unroll
-    for (int j = 0; j < V; ++j) { s[j] = 0.f; q[j] = 0.f; }
-    for (int64_t r = t / lanes_per_row; r < rows; r += rstride) {
-      Vec<dev_t, V> xv = vload<dev_t, V>(x + r * C + c0);
+    for (int u = 0; u < U; ++u) d[u] = load(r + u * p.rstride);
 #pragma unroll
-      for (int j = 0; j < V; ++j) {
-        const float f = to_f32(xv.v[j]);
-        s[j] += f;
-        q[j] += f * f;
+    for (int u = 0; u < U; ++u) add(r + u * p.rstride, d[u]);
+  }
+  for (; r < rows; r += p.rstride) add(r, load(r));
+}
+
+// The shared tail: acc[s][j] is this thread's partial of sum s for channel
+// c0 + j (zero in inactive threads). Every thread of the block must call it.
+template <int V, int NS>
+__device__ __forceinline__ void nhwc_red_tail(const float (&acc)[NS][V],
+                                              float* __restrict__ slab, int C,
+                                              int bl, int rb) {
+  __shared__ __attribute__((aligned(16))) float ls[kRedThreads * V];
+  const int W = bl * V;  // channels of this block, <= kRedLanes * V
+  const int cbase = blockIdx.x * W;
+  float* out = slab + (int64_t)blockIdx.y * NS * C;
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    if (s) __syncthreads();  // the previous sum's reads are done
+    if ((int)threadIdx.x < bl * rb) {  // (rl, lane) sits at rl*W + lane*V
+#pragma unroll
+      for (int j = 0; j < V; ++j) ls[threadIdx.x * V + j] = acc[s][j];
+    }
+    __syncthreads();
+    for (int col = threadIdx.x; col < W; col += kRedThreads) {
+      if (cbase + col < C) {
+        float sum = 0.f;
+        for (int r = 0; r < rb; ++r) sum += ls[r * W + col];
+        out[s * C + cbase + col] = sum;
       }
     }
-#pragma unroll
-    for (int j = 0; j < V; ++j) {
-      atomicAdd(&ls[c0 + j], s[j]);
-      atomicAdd(&ls[C + c0 + j], q[j]);
-    }
   }
+}
+
+// Sums the rows of a [n_parts, n_cols] slab per column into sums[n_cols]:
+// row-lane rl adds rows rl, rl + kSlabRows, ... in ascending order, then a
+// fixed tree over the row-lanes.
+constexpr int kSlabCols = 32, kSlabRows = 32;
+
+__global__ void __launch_bounds__(kSlabCols * kSlabRows)
+bn_slab_reduce_kernel(const float* __restrict__ slab, int n_parts, int n_cols,
+                      float* __restrict__ sums) {
+  __shared__ float ls[kSlabRows][kSlabCols + 1];
+  const int cl = threadIdx.x % kSlabCols, rl = threadIdx.x / kSlabCols;
+  const int c = blockIdx.x * kSlabCols + cl;
+  float s = 0.f;
+  if (c < n_cols) {
+#pragma unroll 4
+    for (int r = rl; r < n_parts; r += kSlabRows)
+      s += slab[(int64_t)r * n_cols + c];
+  }
+  ls[rl][cl] = s;
   __syncthreads();
-  for (int i = threadIdx.x; i < 2 * C; i += blockDim.x)
-    atomicAdd(&sums[i], ls[i]);
+  for (int h = kSlabRows / 2; h > 0; h >>= 1) {
+    if (rl < h) ls[rl][cl] += ls[rl + h][cl];
+    __syncthreads();
+  }
+  if (rl == 0 && c < n_cols) sums[c] = ls[0][cl];
+}
+
+template <typename dev_t, int V>
+__global__ void DLA_RED_KERNEL
+bn_stats_nhwc_kernel(const dev_t* __restrict__ x, float* __restrict__ slab,
+                     int C, int64_t rows, int bl, int rb) {
+  const NhwcRedPos p = nhwc_red_pos<V>(C, bl, rb);
+  float acc[2][V];  // sum, sumsq
+#pragma unroll
+  for (int j = 0; j < V; ++j) { acc[0][j] = 0.f; acc[1][j] = 0.f; }
+  nhwc_red_rows<red_unroll(1)>(
+      p, rows, [&](int64_t r) { return vload<dev_t, V>(x + r * C + p.c0); },
+      [&](int64_t, const Vec<dev_t, V>& xv) {
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+          const float f = to_f32(xv.v[j]);
+          acc[0][j] += f;
+          acc[1][j] += f * f;
+        }
+      });
+  nhwc_red_tail<V, 2>(acc, slab, C, bl, rb);
 }
 
 template <typename dev_t, int V, bool RELU>
@@ -292,59 +417,54 @@ __global__ void bn_apply_nhwc_kernel(const dev_t* __restrict__ x,
 // bn_pre(x, scale, shift) is not > 0; y is neither passed nor loaded) or, for
 // A/B runs and callers of the old entry point, from the stored y (MASK_Y).
 template <typename dev_t, int V, bool RELU, bool MASK_Y = false>
-__global__ void bn_bwd_stats_nhwc_kernel(const dev_t* __restrict__ dy,
-                                         const dev_t* __restrict__ x,
-                                         const dev_t* __restrict__ y,
-                                         const float* __restrict__ scale,
-                                         const float* __restrict__ shift,
-                                         const float* __restrict__ mean,
-                                         const float* __restrict__ rstd,
-                                         float* __restrict__ sums, int C,
-                                         int64_t rows, int64_t used) {
-  extern __shared__ float ls[];
-  for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) ls[i] = 0.f;
-  __syncthreads();
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int lanes_per_row = C / V;
-  if (t < used) {
-    const int c0 = (int)(t % lanes_per_row) * V;
-    const int64_t rstride = used / lanes_per_row;
-    float mu[V], rs[V], sc[V], sh[V], s_dy[V], s_dyxh[V];
+__global__ void DLA_RED_KERNEL
+bn_bwd_stats_nhwc_kernel(const dev_t* __restrict__ dy,
+                         const dev_t* __restrict__ x,
+                         const dev_t* __restrict__ y,
+                         const float* __restrict__ scale,
+                         const float* __restrict__ shift,
+                         const float* __restrict__ mean,
+                         const float* __restrict__ rstd,
+                         float* __restrict__ slab, int C, int64_t rows, int bl,
+                         int rb) {
+  const NhwcRedPos p = nhwc_red_pos<V>(C, bl, rb);
+  float mu[V], rs[V], sc[V], sh[V];
+  float acc[2][V];  // sum dy, sum dy*xhat
 #pragma unroll
-    for (int j = 0; j < V; ++j) {
-      mu[j] = mean[c0 + j];
-      rs[j] = rstd[c0 + j];
-      sc[j] = (RELU && !MASK_Y) ? scale[c0 + j] : 0.f;
-      sh[j] = (RELU && !MASK_Y) ? shift[c0 + j] : 0.f;
-      s_dy[j] = 0.f;
-      s_dyxh[j] = 0.f;
-    }
-    for (int64_t r = t / lanes_per_row; r < rows; r += rstride) {
-      const int64_t base = r * C + c0;
-      Vec<dev_t, V> dyv = vload<dev_t, V>(dy + base);
-      Vec<dev_t, V> xv = vload<dev_t, V>(x + base);
-      Vec<dev_t, V> yv;
-      if (RELU && MASK_Y) yv = vload<dev_t, V>(y + base);
-#pragma unroll
-      for (int j = 0; j < V; ++j) {
-        float g = to_f32(dyv.v[j]);
-        const float xf = to_f32(xv.v[j]);
-        if (RELU && MASK_Y && to_f32(yv.v[j]) <= 0.f) g = 0.f;
-        if (RELU && !MASK_Y && !(bn_pre(xf, sc[j], sh[j]) > 0.f)) g = 0.f;
-        const float xh = (xf - mu[j]) * rs[j];
-        s_dy[j] += g;
-        s_dyxh[j] += g * xh;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < V; ++j) {
-      atomicAdd(&ls[c0 + j], s_dy[j]);
-      atomicAdd(&ls[C + c0 + j], s_dyxh[j]);
-    }
+  for (int j = 0; j < V; ++j) {
+    mu[j] = p.active ? mean[p.c0 + j] : 0.f;
+    rs[j] = p.active ? rstd[p.c0 + j] : 0.f;
+    sc[j] = (p.active && RELU && !MASK_Y) ? scale[p.c0 + j] : 0.f;
+    sh[j] = (p.active && RELU && !MASK_Y) ? shift[p.c0 + j] : 0.f;
+    acc[0][j] = 0.f;
+    acc[1][j] = 0.f;
   }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 2 * C; i += blockDim.x)
-    atomicAdd(&sums[i], ls[i]);
+  struct Row {
+    Vec<dev_t, V> dy, x, y;
+  };
+  nhwc_red_rows<red_unroll(MASK_Y ? 3 : 2)>(
+      p, rows,
+      [&](int64_t r) {
+        const int64_t base = r * C + p.c0;
+        Row d;
+        d.dy = vload<dev_t, V>(dy + base);
+        d.x = vload<dev_t, V>(x + base);
+        if (RELU && MASK_Y) d.y = vload<dev_t, V>(y + base);
+        return d;
+      },
+      [&](int64_t, const Row& d) {
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+          float g = to_f32(d.dy.v[j]);
+          const float xf = to_f32(d.x.v[j]);
+          if (RELU && MASK_Y && to_f32(d.y.v[j]) <= 0.f) g = 0.f;
+          if (RELU && !MASK_Y && !(bn_pre(xf, sc[j], sh[j]) > 0.f)) g = 0.f;
+          const float xh = (xf - mu[j]) * rs[j];
+          acc[0][j] += g;
+          acc[1][j] += g * xh;
+        }
+      });
+  nhwc_red_tail<V, 2>(acc, slab, C, bl, rb);
 }
 
 template <typename dev_t, int V, bool RELU, bool MASK_Y = false>
@@ -444,62 +564,56 @@ __global__ void bn_add_relu_nhwc_kernel(const dev_t* __restrict__ x,
 // (DUAL: also sum(g*xhat_d)) reduce per channel through LDS.
 // sums layout: {sum g [C], sum g*xhat [C], sum g*xhat_d [C] (DUAL)}.
 template <typename dev_t, int V, bool DUAL>
-__global__ void bn_join_bwd_stats_nhwc_kernel(
+__global__ void DLA_RED_KERNEL
+bn_join_bwd_stats_nhwc_kernel(
     const dev_t* __restrict__ dy, const dev_t* __restrict__ out,
     const dev_t* __restrict__ x, const float* __restrict__ mean,
     const float* __restrict__ rstd, const dev_t* __restrict__ xd,
     const float* __restrict__ mean_d, const float* __restrict__ rstd_d,
-    dev_t* __restrict__ g_out, float* __restrict__ sums, int C, int64_t rows,
-    int64_t used) {
+    dev_t* __restrict__ g_out, float* __restrict__ slab, int C, int64_t rows,
+    int bl, int rb) {
   constexpr int NS = DUAL ? 3 : 2;
-  extern __shared__ float ls[];  // NS*C floats
-  for (int i = threadIdx.x; i < NS * C; i += blockDim.x) ls[i] = 0.f;
-  __syncthreads();
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int lanes_per_row = C / V;
-  if (t < used) {
-    const int c0 = (int)(t % lanes_per_row) * V;
-    const int64_t rstride = used / lanes_per_row;
-    float mu[V], rs[V], mud[V], rsd[V], s_g[V], s_gxh[V], s_gxhd[V];
+  const NhwcRedPos p = nhwc_red_pos<V>(C, bl, rb);
+  float mu[V], rs[V], mud[V], rsd[V];
+  float acc[NS][V];  // sum g, sum g*xhat, (DUAL) sum g*xhat_d
 #pragma unroll
-    for (int j = 0; j < V; ++j) {
-      mu[j] = mean[c0 + j];
-      rs[j] = rstd[c0 + j];
-      mud[j] = DUAL ? mean_d[c0 + j] : 0.f;
-      rsd[j] = DUAL ? rstd_d[c0 + j] : 0.f;
-      s_g[j] = 0.f;
-      s_gxh[j] = 0.f;
-      s_gxhd[j] = 0.f;
-    }
-    for (int64_t r = t / lanes_per_row; r < rows; r += rstride) {
-      const int64_t base = r * C + c0;
-      Vec<dev_t, V> dyv = vload<dev_t, V>(dy + base);
-      Vec<dev_t, V> ov = vload<dev_t, V>(out + base);
-      Vec<dev_t, V> xv = vload<dev_t, V>(x + base);
-      Vec<dev_t, V> xdv;
-      if (DUAL) xdv = vload<dev_t, V>(xd + base);
-      Vec<dev_t, V> gv;
+  for (int j = 0; j < V; ++j) {
+    mu[j] = p.active ? mean[p.c0 + j] : 0.f;
+    rs[j] = p.active ? rstd[p.c0 + j] : 0.f;
+    mud[j] = (p.active && DUAL) ? mean_d[p.c0 + j] : 0.f;
+    rsd[j] = (p.active && DUAL) ? rstd_d[p.c0 + j] : 0.f;
 #pragma unroll
-      for (int j = 0; j < V; ++j) {
-        const bool on = to_f32(ov.v[j]) > 0.f;
-        gv.v[j] = on ? dyv.v[j] : from_f32<dev_t>(0.f);
-        const float g = on ? to_f32(dyv.v[j]) : 0.f;
-        s_g[j] += g;
-        s_gxh[j] += g * ((to_f32(xv.v[j]) - mu[j]) * rs[j]);
-        if (DUAL) s_gxhd[j] += g * ((to_f32(xdv.v[j]) - mud[j]) * rsd[j]);
-      }
-      vstore<dev_t, V>(g_out + base, gv);
-    }
-#pragma unroll
-    for (int j = 0; j < V; ++j) {
-      atomicAdd(&ls[c0 + j], s_g[j]);
-      atomicAdd(&ls[C + c0 + j], s_gxh[j]);
-      if (DUAL) atomicAdd(&ls[2 * C + c0 + j], s_gxhd[j]);
-    }
+    for (int s = 0; s < NS; ++s) acc[s][j] = 0.f;
   }
-  __syncthreads();
-  for (int i = threadIdx.x; i < NS * C; i += blockDim.x)
-    atomicAdd(&sums[i], ls[i]);
+  struct Row {
+    Vec<dev_t, V> dy, out, x, xd;
+  };
+  nhwc_red_rows<red_unroll(DUAL ? 4 : 3)>(
+      p, rows,
+      [&](int64_t r) {
+        const int64_t base = r * C + p.c0;
+        Row d;
+        d.dy = vload<dev_t, V>(dy + base);
+        d.out = vload<dev_t, V>(out + base);
+        d.x = vload<dev_t, V>(x + base);
+        if (DUAL) d.xd = vload<dev_t, V>(xd + base);
+        return d;
+      },
+      [&](int64_t r, const Row& d) {
+        Vec<dev_t, V> gv;
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+          const bool on = to_f32(d.out.v[j]) > 0.f;
+          gv.v[j] = on ? d.dy.v[j] : from_f32<dev_t>(0.f);
+          const float g = on ? to_f32(d.dy.v[j]) : 0.f;
+          acc[0][j] += g;
+          acc[1][j] += g * ((to_f32(d.x.v[j]) - mu[j]) * rs[j]);
+          if (DUAL)
+            acc[NS - 1][j] += g * ((to_f32(d.xd.v[j]) - mud[j]) * rsd[j]);
+        }
+        vstore<dev_t, V>(g_out + r * C + p.c0, gv);
+      });
+  nhwc_red_tail<V, NS>(acc, slab, C, bl, rb);
 }
 
 // Dual join backward pass 2: one read of g feeds both BNs' dx.
@@ -610,6 +724,19 @@ inline torch::Tensor bn_param_grad(const torch::Tensor& sums, int64_t offset,
   return sums.narrow(0, offset, C).to(weight.scalar_type());
 }
 
+// Backward: the [n_parts, NS*C] slab of a reduction kernel summed into a
+// fresh [NS*C] tensor, which the dx kernels read and bn_param_grad views.
+inline torch::Tensor bn_slab_reduce_launch(const torch::Tensor& slab) {
+  const int n_parts = (int)slab.size(0), n_cols = (int)slab.size(1);
+  auto sums = torch::empty({n_cols}, slab.options());
+  hipLaunchKernelGGL(bn_slab_reduce_kernel,
+                     dim3((n_cols + kSlabCols - 1) / kSlabCols),
+                     dim3(kSlabCols * kSlabRows), 0, stream(),
+                     slab.data_ptr<float>(), n_parts, n_cols,
+                     sums.data_ptr<float>());
+  return sums;
+}
+
 inline bool is_nhwc_rows(const torch::Tensor& t) {
   return t.dim() == 4 && t.is_contiguous(at::MemoryFormat::ChannelsLast);
 }
@@ -632,7 +759,9 @@ std::vector<torch::Tensor> batchnorm_fwd(torch::Tensor x, torch::Tensor weight,
   const int N = (int)x.size(0), C = (int)x.size(1);
   const int64_t HW = x.size(2) * x.size(3);
   auto opts_f = x.options().dtype(torch::kFloat);
-  auto sums = torch::zeros({2 * C}, opts_f);
+  // NCHW: the zeroed [2C] vector that bn_stats_kernel adds into. NHWC: the
+  // stats kernel's [n_parts, 2C] slab, summed by the finalize kernel.
+  auto sums = nhwc ? torch::Tensor() : torch::zeros({2 * C}, opts_f);
   auto mean = torch::empty({C}, opts_f);
   auto rstd = torch::empty({C}, opts_f);
   auto scale = torch::empty({C}, opts_f);
@@ -649,13 +778,12 @@ std::vector<torch::Tensor> batchnorm_fwd(torch::Tensor x, torch::Tensor weight,
       constexpr int VM = 16 / (int)sizeof(dev_t);
       auto stats = [&](auto vtag) {
         constexpr int V = decltype(vtag)::value;
-        const int lanes = C / V;
-        const int64_t used = dla::nhwc_used_threads(lanes, rows, 262144);
-        const int lds = 2 * C * sizeof(float);
+        const auto t = dla::nhwc_red_tile(C / V, rows);
+        sums = torch::empty({t.parts, 2 * C}, opts_f);
         hipLaunchKernelGGL((dla::bn_stats_nhwc_kernel<dev_t, V>),
-                           dim3((int)((used + 255) / 256)), dim3(256), lds,
+                           dim3(t.chunks, t.parts), dim3(dla::kRedThreads), 0,
                            dla::stream(), (const dev_t*)x.data_ptr(),
-                           sums.data_ptr<float>(), C, rows, used);
+                           sums.data_ptr<float>(), C, rows, t.bl, t.rb);
       };
       if (C % VM == 0) stats(std::integral_constant<int, VM>{});
       else if (C % 2 == 0) stats(std::integral_constant<int, 2>{});
@@ -665,14 +793,25 @@ std::vector<torch::Tensor> batchnorm_fwd(torch::Tensor x, torch::Tensor weight,
                          dla::stream(), (const dev_t*)x.data_ptr(),
                          sums.data_ptr<float>(), N, C, HW);
     }
-    hipLaunchKernelGGL(dla::bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0,
-                       dla::stream(), sums.data_ptr<float>(), w32.data_ptr<float>(),
-                       b32.data_ptr<float>(), mean.data_ptr<float>(),
-                       rstd.data_ptr<float>(),
-                       running_mean.has_value() ? running_mean->data_ptr<float>() : nullptr,
-                       running_var.has_value() ? running_var->data_ptr<float>() : nullptr,
-                       scale.data_ptr<float>(), shift.data_ptr<float>(), C,
-                       (float)rows, (float)eps, (float)momentum);
+    float* rm = running_mean.has_value() ? running_mean->data_ptr<float>() : nullptr;
+    float* rv = running_var.has_value() ? running_var->data_ptr<float>() : nullptr;
+    if (sums.dim() == 2 && sums.size(0) > 1) {
+      hipLaunchKernelGGL(dla::bn_finalize_parts_kernel,
+                         dim3((C + dla::kFinCh - 1) / dla::kFinCh),
+                         dim3(dla::kFinCh * dla::kFinRows), 0, dla::stream(),
+                         sums.data_ptr<float>(), (int)sums.size(0),
+                         w32.data_ptr<float>(), b32.data_ptr<float>(),
+                         mean.data_ptr<float>(), rstd.data_ptr<float>(), rm, rv,
+                         scale.data_ptr<float>(), shift.data_ptr<float>(), C,
+                         (float)rows, (float)eps, (float)momentum);
+    } else {
+      hipLaunchKernelGGL(dla::bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0,
+                         dla::stream(), sums.data_ptr<float>(), w32.data_ptr<float>(),
+                         b32.data_ptr<float>(), mean.data_ptr<float>(),
+                         rstd.data_ptr<float>(), rm, rv,
+                         scale.data_ptr<float>(), shift.data_ptr<float>(), C,
+                         (float)rows, (float)eps, (float)momentum);
+    }
     const int64_t n_total = x.numel();
     constexpr int VMAX = 16 / (int)sizeof(dev_t);
     auto launch = [&](auto vtag, auto rtag) {
@@ -843,7 +982,8 @@ std::vector<torch::Tensor> batchnorm_bwd_ex(
   const int64_t HW = x.size(2) * x.size(3);
   const int64_t rows = (int64_t)N * HW;
   auto opts_f = x.options().dtype(torch::kFloat);
-  auto sums = torch::zeros({2 * C}, opts_f);
+  // NCHW: zeroed, bn_bwd_stats_kernel adds. NHWC: the slab's fixed-order sum.
+  auto sums = nhwc ? torch::Tensor() : torch::zeros({2 * C}, opts_f);
   auto dx = torch::empty_like(x);
   auto w32 = weight.to(torch::kFloat);
   const int ysplit = (int)std::min<int64_t>((rows + 65535) / 65536 + 1,
@@ -879,15 +1019,15 @@ std::vector<torch::Tensor> batchnorm_bwd_ex(
         constexpr int VM = 16 / (int)sizeof(dev_t);
         auto stats = [&](auto vtag) {
           constexpr int V = decltype(vtag)::value;
-          const int lanes = C / V;
-          const int64_t used = dla::nhwc_used_threads(lanes, rows, 262144);
-          const int lds = 2 * C * sizeof(float);
+          const auto t = dla::nhwc_red_tile(C / V, rows);
+          auto slab = torch::empty({t.parts, 2 * C}, opts_f);
           hipLaunchKernelGGL((dla::bn_bwd_stats_nhwc_kernel<dev_t, V, R, MY>),
-                             dim3((int)((used + 255) / 256)), dim3(256), lds,
-                             dla::stream(), (const dev_t*)dy.data_ptr(),
+                             dim3(t.chunks, t.parts), dim3(dla::kRedThreads),
+                             0, dla::stream(), (const dev_t*)dy.data_ptr(),
                              (const dev_t*)x.data_ptr(), yp, scp, shp,
                              mean.data_ptr<float>(), rstd.data_ptr<float>(),
-                             sums.data_ptr<float>(), C, rows, used);
+                             slab.data_ptr<float>(), C, rows, t.bl, t.rb);
+          sums = dla::bn_slab_reduce_launch(slab);
         };
         if (C % VM == 0) stats(std::integral_constant<int, VM>{});
         else if (C % 2 == 0) stats(std::integral_constant<int, 2>{});
@@ -1047,22 +1187,25 @@ std::vector<torch::Tensor> bn_add_relu_bwd(torch::Tensor dy, torch::Tensor out,
   const int64_t rows = x.numel() / C;
   TORCH_CHECK(mean.numel() == C && rstd.numel() == C && weight.numel() == C,
               "bn_add_relu_bwd: per-channel tensors must have C elements");
-  auto sums = torch::zeros({2 * C}, x.options().dtype(torch::kFloat));
+  torch::Tensor sums;
   auto g = torch::empty_like(x);
   auto dx = torch::empty_like(x);
   auto w32 = weight.to(torch::kFloat).contiguous();
   DLA_DISPATCH_FLOAT_TYPES(x.scalar_type(), "bn_add_relu_bwd", [&] {
     constexpr int V = 16 / (int)sizeof(dev_t);
     const int lanes = C / V;
-    const int64_t used_s = dla::nhwc_used_threads(lanes, rows, 262144);
+    const auto t = dla::nhwc_red_tile(lanes, rows);
+    auto slab = torch::empty({t.parts, 2 * C},
+                             x.options().dtype(torch::kFloat));
     hipLaunchKernelGGL((dla::bn_join_bwd_stats_nhwc_kernel<dev_t, V, false>),
-                       dim3((int)((used_s + 255) / 256)), dim3(256),
-                       2 * C * sizeof(float), dla::stream(),
+                       dim3(t.chunks, t.parts), dim3(dla::kRedThreads), 0,
+                       dla::stream(),
                        (const dev_t*)dy.data_ptr(), (const dev_t*)out.data_ptr(),
                        (const dev_t*)x.data_ptr(), mean.data_ptr<float>(),
                        rstd.data_ptr<float>(), nullptr, nullptr, nullptr,
-                       (dev_t*)g.data_ptr(), sums.data_ptr<float>(), C, rows,
-                       used_s);
+                       (dev_t*)g.data_ptr(), slab.data_ptr<float>(), C, rows,
+                       t.bl, t.rb);
+    sums = dla::bn_slab_reduce_launch(slab);
     const int64_t used = dla::nhwc_used_threads(lanes, rows, 524288);
     hipLaunchKernelGGL((dla::bn_bwd_dx_nhwc_kernel<dev_t, V, false>),
                        dim3((int)((used + 255) / 256)), dim3(256), 0,
@@ -1097,7 +1240,7 @@ std::vector<torch::Tensor> bn_add_relu_dual_bwd(
                   mean_d.numel() == C && rstd_d.numel() == C &&
                   weight_d.numel() == C,
               "bn_add_relu_dual_bwd: per-channel tensors must have C elements");
-  auto sums = torch::zeros({3 * C}, x.options().dtype(torch::kFloat));
+  torch::Tensor sums;
   auto g = torch::empty_like(x);
   auto dx = torch::empty_like(x);
   auto dxd = torch::empty_like(x);
@@ -1106,16 +1249,19 @@ std::vector<torch::Tensor> bn_add_relu_dual_bwd(
   DLA_DISPATCH_FLOAT_TYPES(x.scalar_type(), "bn_add_relu_dual_bwd", [&] {
     constexpr int V = 16 / (int)sizeof(dev_t);
     const int lanes = C / V;
-    const int64_t used_s = dla::nhwc_used_threads(lanes, rows, 262144);
+    const auto t = dla::nhwc_red_tile(lanes, rows);
+    auto slab = torch::empty({t.parts, 3 * C},
+                             x.options().dtype(torch::kFloat));
     hipLaunchKernelGGL((dla::bn_join_bwd_stats_nhwc_kernel<dev_t, V, true>),
-                       dim3((int)((used_s + 255) / 256)), dim3(256),
-                       3 * C * sizeof(float), dla::stream(),
+                       dim3(t.chunks, t.parts), dim3(dla::kRedThreads), 0,
+                       dla::stream(),
                        (const dev_t*)dy.data_ptr(), (const dev_t*)out.data_ptr(),
                        (const dev_t*)x.data_ptr(), mean.data_ptr<float>(),
                        rstd.data_ptr<float>(), (const dev_t*)xd.data_ptr(),
                        mean_d.data_ptr<float>(), rstd_d.data_ptr<float>(),
-                       (dev_t*)g.data_ptr(), sums.data_ptr<float>(), C, rows,
-                       used_s);
+                       (dev_t*)g.data_ptr(), slab.data_ptr<float>(), C, rows,
+                       t.bl, t.rb);
+    sums = dla::bn_slab_reduce_launch(slab);
     const int64_t used = dla::nhwc_used_threads(lanes, rows, 524288);
     hipLaunchKernelGGL((dla::bn_join_bwd_dx_dual_nhwc_kernel<dev_t, V>),
                        dim3((int)((used + 255) / 256)), dim3(256), 0,
@@ -1248,57 +1394,51 @@ __device__ __forceinline__ void stem_pool_grad(
 }
 
 // Backward pass 1: sum g, sum g*xhat per channel; thread mapping and the
-// LDS-then-global-atomics reduction are bn_bwd_stats_nhwc_kernel's.
+// slab tail are bn_bwd_stats_nhwc_kernel's. The gathers of stem_pool_grad
+// depend on one another, so this kernel waits on latency, not on bandwidth:
+// no row unroll and no occupancy cap (fewer registers, more waves), and a
+// grid of kStemRedBlocks blocks.
+constexpr int kStemRedBlocks = 1024;
+
 template <typename dev_t, int V>
-__global__ void bn_relu_maxpool_bwd_stats_nhwc_kernel(
+__global__ void __launch_bounds__(kRedThreads)
+bn_relu_maxpool_bwd_stats_nhwc_kernel(
     const dev_t* __restrict__ dpool, const uint8_t* __restrict__ slots,
     const dev_t* __restrict__ x, const float* __restrict__ scale,
     const float* __restrict__ shift, const float* __restrict__ mean,
-    const float* __restrict__ rstd, float* __restrict__ sums, int C, int H,
-    int W, int OH, int OW, int64_t rows, int64_t used) {
-  extern __shared__ float ls[];
-  for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) ls[i] = 0.f;
-  __syncthreads();
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int lanes_per_row = C / V;
-  if (t < used) {
-    const int c0 = (int)(t % lanes_per_row) * V;
-    const int64_t rstride = used / lanes_per_row;
-    float mu[V], rs[V], sc[V], sh[V], s_g[V], s_gxh[V], g[V];
+    const float* __restrict__ rstd, float* __restrict__ slab, int C, int H,
+    int W, int OH, int OW, int64_t rows, int bl, int rb) {
+  const NhwcRedPos p = nhwc_red_pos<V>(C, bl, rb);
+  float mu[V], rs[V], sc[V], sh[V];
+  float acc[2][V];  // sum g, sum g*xhat
 #pragma unroll
-    for (int j = 0; j < V; ++j) {
-      mu[j] = mean[c0 + j];
-      rs[j] = rstd[c0 + j];
-      sc[j] = scale[c0 + j];
-      sh[j] = shift[c0 + j];
-      s_g[j] = 0.f;
-      s_gxh[j] = 0.f;
-    }
-    for (int64_t r = t / lanes_per_row; r < rows; r += rstride) {
-      const uint32_t r32 = (uint32_t)r;  // rows < 2^31 (checked by the host)
-      const uint32_t q = r32 / (uint32_t)W;
-      const int w = (int)(r32 - q * (uint32_t)W);
-      const int n = (int)(q / (uint32_t)H);
-      const int h = (int)(q - (uint32_t)n * (uint32_t)H);
-      Vec<dev_t, V> xv = vload<dev_t, V>(x + r * C + c0);
-      stem_pool_grad<dev_t, V>(dpool, slots, xv, sc, sh, n, h, w, c0, C, OH,
-                               OW, g);
-#pragma unroll
-      for (int j = 0; j < V; ++j) {
-        const float xh = (to_f32(xv.v[j]) - mu[j]) * rs[j];
-        s_g[j] += g[j];
-        s_gxh[j] += g[j] * xh;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < V; ++j) {
-      atomicAdd(&ls[c0 + j], s_g[j]);
-      atomicAdd(&ls[C + c0 + j], s_gxh[j]);
-    }
+  for (int j = 0; j < V; ++j) {
+    mu[j] = p.active ? mean[p.c0 + j] : 0.f;
+    rs[j] = p.active ? rstd[p.c0 + j] : 0.f;
+    sc[j] = p.active ? scale[p.c0 + j] : 0.f;
+    sh[j] = p.active ? shift[p.c0 + j] : 0.f;
+    acc[0][j] = 0.f;
+    acc[1][j] = 0.f;
   }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 2 * C; i += blockDim.x)
-    atomicAdd(&sums[i], ls[i]);
+  nhwc_red_rows<1>(
+      p, rows, [&](int64_t r) { return vload<dev_t, V>(x + r * C + p.c0); },
+      [&](int64_t r, const Vec<dev_t, V>& xv) {
+        const uint32_t r32 = (uint32_t)r;  // rows < 2^31 (checked by the host)
+        const uint32_t q = r32 / (uint32_t)W;
+        const int w = (int)(r32 - q * (uint32_t)W);
+        const int n = (int)(q / (uint32_t)H);
+        const int h = (int)(q - (uint32_t)n * (uint32_t)H);
+        float g[V];
+        stem_pool_grad<dev_t, V>(dpool, slots, xv, sc, sh, n, h, w, p.c0, C,
+                                 OH, OW, g);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+          const float xh = (to_f32(xv.v[j]) - mu[j]) * rs[j];
+          acc[0][j] += g[j];
+          acc[1][j] += g[j] * xh;
+        }
+      });
+  nhwc_red_tail<V, 2>(acc, slab, C, bl, rb);
 }
 
 // Backward pass 2: dx = weight*rstd*(g - mean(g) - xhat*mean(g*xhat)).
@@ -1367,7 +1507,6 @@ std::vector<torch::Tensor> bn_relu_maxpool_fwd(
   const int H = (int)x.size(2), W = (int)x.size(3);
   const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
   const int64_t rows = (int64_t)N * H * W;
-  auto sums = torch::zeros({2 * C}, x.options().dtype(torch::kFloat));
   auto out_opts = x.options().memory_format(at::MemoryFormat::ChannelsLast);
   auto pooled = torch::empty({N, C, OH, OW}, out_opts);
   auto slots = torch::empty({N, C, OH, OW}, out_opts.dtype(torch::kByte));
@@ -1377,12 +1516,13 @@ std::vector<torch::Tensor> bn_relu_maxpool_fwd(
   dla::BnFinalized fin;
   DLA_DISPATCH_FLOAT_TYPES(x.scalar_type(), "bn_relu_maxpool_fwd", [&] {
     constexpr int V = 16 / (int)sizeof(dev_t);
-    const int64_t used = dla::nhwc_used_threads(C / V, rows, 262144);
+    const auto t = dla::nhwc_red_tile(C / V, rows);
+    auto sums = torch::empty({t.parts, 2 * C},
+                             x.options().dtype(torch::kFloat));
     hipLaunchKernelGGL((dla::bn_stats_nhwc_kernel<dev_t, V>),
-                       dim3((int)((used + 255) / 256)), dim3(256),
-                       2 * C * sizeof(float), dla::stream(),
-                       (const dev_t*)x.data_ptr(), sums.data_ptr<float>(), C,
-                       rows, used);
+                       dim3(t.chunks, t.parts), dim3(dla::kRedThreads), 0,
+                       dla::stream(), (const dev_t*)x.data_ptr(),
+                       sums.data_ptr<float>(), C, rows, t.bl, t.rb);
     fin = dla::bn_finalize_launch(sums, weight, bias, running_mean,
                                   running_var, C, rows, momentum, eps);
     hipLaunchKernelGGL((dla::bn_relu_maxpool_fwd_nhwc_kernel<dev_t, V>),
@@ -1423,21 +1563,25 @@ std::vector<torch::Tensor> bn_relu_maxpool_bwd(
                 "bn_relu_maxpool_bwd: per-channel tensors must be contiguous "
                 "fp32 [C]");
   TORCH_CHECK(weight.numel() == C, "bn_relu_maxpool_bwd: weight must be [C]");
-  auto sums = torch::zeros({2 * C}, x.options().dtype(torch::kFloat));
+  torch::Tensor sums;
   auto dx = torch::empty_like(x);
   auto w32 = weight.to(torch::kFloat).contiguous();
   DLA_DISPATCH_FLOAT_TYPES(x.scalar_type(), "bn_relu_maxpool_bwd", [&] {
     constexpr int V = 16 / (int)sizeof(dev_t);
     const int lanes = C / V;
-    const int64_t used_s = dla::nhwc_used_threads(lanes, rows, 262144);
+    const auto t = dla::nhwc_red_tile(lanes, rows, dla::kStemRedBlocks,
+                                      dla::kStemRedBlocks);
+    auto slab = torch::empty({t.parts, 2 * C},
+                             x.options().dtype(torch::kFloat));
     hipLaunchKernelGGL((dla::bn_relu_maxpool_bwd_stats_nhwc_kernel<dev_t, V>),
-                       dim3((int)((used_s + 255) / 256)), dim3(256),
-                       2 * C * sizeof(float), dla::stream(),
-                       (const dev_t*)dpool.data_ptr(),
+                       dim3(t.chunks, t.parts), dim3(dla::kRedThreads), 0,
+                       dla::stream(), (const dev_t*)dpool.data_ptr(),
                        slots.data_ptr<uint8_t>(), (const dev_t*)x.data_ptr(),
                        scale.data_ptr<float>(), shift.data_ptr<float>(),
                        mean.data_ptr<float>(), rstd.data_ptr<float>(),
-                       sums.data_ptr<float>(), C, H, W, OH, OW, rows, used_s);
+                       slab.data_ptr<float>(), C, H, W, OH, OW, rows, t.bl,
+                       t.rb);
+    sums = dla::bn_slab_reduce_launch(slab);
     const int64_t used = dla::nhwc_used_threads(lanes, rows, 524288);
     hipLaunchKernelGGL((dla::bn_relu_maxpool_bwd_dx_nhwc_kernel<dev_t, V>),
                        dim3((int)((used + 255) / 256)), dim3(256), 0,
