@@ -10,20 +10,8 @@
 
 namespace dla {
 
-// The BN pre-activation x*scale + shift as ONE explicit fused multiply-add.
-// The forward apply kernels and the ReLU mask of the backward kernels both go
-// through this function, so the mask `bn_pre(x, sc, sh) > 0` is decided by the
-// very instruction sequence that produced y.
-//
-// Known edge of masking from x and not from the stored y: the two differ
-// only where a positive fp32 pre-activation rounds to zero in the storage
-// type. bf16 has fp32's exponent range, so that needs a value below bf16's
-// smallest subnormal (~9e-41); for fp16 it is anything below ~3e-8. A NaN
-// pre-activation gives mask 0 on both routes (fmaxf(NaN, 0) = 0 forward,
-// NaN > 0 false backward).
-__device__ __forceinline__ float bn_pre(float x, float sc, float sh) {
-  return fmaf(x, sc, sh);
-}
+// bn_pre (the BN pre-activation, shared with the conv1x1 dgrad epilogue) lives
+// in common.h.
 
 // ---- pass 1: per-channel sum / sumsq ---------------------------------------
 template <typename dev_t>
@@ -364,6 +352,38 @@ bn_slab_reduce_kernel(const float* __restrict__ slab, int n_parts, int n_cols,
     __syncthreads();
   }
   if (rl == 0 && c < n_cols) sums[c] = ls[0][cl];
+}
+
+// First stage for deep slabs (the conv dgrad epilogue leaves one row per 128
+// GEMM rows: 6272 at 56x56, batch 256): block (x, y) sums the kSlabGroup rows
+// of group y for its kSlabCols columns into row y of a [groups, n_cols] slab,
+// in the same order as above; bn_slab_reduce_kernel then sums the groups.
+// groups * n_cols / 32 blocks pull the slab, not n_cols / 32.
+constexpr int kSlabGroup = 128;     // slab rows per first-stage block
+// Slabs deeper than any reduction kernel's own (kRedMaxParts) take two stages.
+constexpr int kSlabDeep = kRedMaxParts;
+
+__global__ void __launch_bounds__(kSlabCols * kSlabRows)
+bn_slab_group_reduce_kernel(const float* __restrict__ slab, int n_parts,
+                            int n_cols, float* __restrict__ groups) {
+  __shared__ float ls[kSlabRows][kSlabCols + 1];
+  const int cl = threadIdx.x % kSlabCols, rl = threadIdx.x / kSlabCols;
+  const int c = blockIdx.x * kSlabCols + cl;
+  const int r0 = blockIdx.y * kSlabGroup;
+  const int r1 = r0 + kSlabGroup < n_parts ? r0 + kSlabGroup : n_parts;
+  float s = 0.f;
+  if (c < n_cols) {
+#pragma unroll 4
+    for (int r = r0 + rl; r < r1; r += kSlabRows)
+      s += slab[(int64_t)r * n_cols + c];
+  }
+  ls[rl][cl] = s;
+  __syncthreads();
+  for (int h = kSlabRows / 2; h > 0; h >>= 1) {
+    if (rl < h) ls[rl][cl] += ls[rl + h][cl];
+    __syncthreads();
+  }
+  if (rl == 0 && c < n_cols) groups[(int64_t)blockIdx.y * n_cols + c] = ls[0][cl];
 }
 
 template <typename dev_t, int V>
@@ -728,6 +748,16 @@ inline torch::Tensor bn_param_grad(const torch::Tensor& sums, int64_t offset,
 // fresh [NS*C] tensor, which the dx kernels read and bn_param_grad views.
 inline torch::Tensor bn_slab_reduce_launch(const torch::Tensor& slab) {
   const int n_parts = (int)slab.size(0), n_cols = (int)slab.size(1);
+  if (n_parts > kSlabDeep) {  // two stages, both in a fixed order
+    const int groups = (n_parts + kSlabGroup - 1) / kSlabGroup;
+    auto part = torch::empty({groups, n_cols}, slab.options());
+    hipLaunchKernelGGL(bn_slab_group_reduce_kernel,
+                       dim3((n_cols + kSlabCols - 1) / kSlabCols, groups),
+                       dim3(kSlabCols * kSlabRows), 0, stream(),
+                       slab.data_ptr<float>(), n_parts, n_cols,
+                       part.data_ptr<float>());
+    return bn_slab_reduce_launch(part);
+  }
   auto sums = torch::empty({n_cols}, slab.options());
   hipLaunchKernelGGL(bn_slab_reduce_kernel,
                      dim3((n_cols + kSlabCols - 1) / kSlabCols),
@@ -1277,6 +1307,109 @@ std::vector<torch::Tensor> bn_add_relu_dual_bwd(
   HIP_CHECK_ERR();
   // sum g serves both biases, but two parameters must not share gradient
   // storage (optimizers update .grad in place): the second gets a copy
+  auto dbias = dla::bn_param_grad(sums, 0, C, weight);
+  return {dx, dxd, dla::bn_param_grad(sums, C, C, weight), dbias,
+          dla::bn_param_grad(sums, 2 * C, C, weight_d),
+          dbias.to(weight_d.scalar_type()).clone()};
+}
+
+// ---- dx-only backward: pass 1 ran in the conv1x1 dgrad epilogue -------------
+// g is the masked gradient that epilogue stored and slab its [n_parts, NS*C]
+// partial sums (conv1x1_dgrad_bwdstats), so what is left is the slab reduce
+// and the dx pass. Serves BatchNorm(+ReLU) and the single join alike: with the
+// mask already in g both are bn_bwd_dx_nhwc_kernel<.., false>.
+namespace dla {
+
+inline void dx_only_check(const torch::Tensor& x, const torch::Tensor& g,
+                          const torch::Tensor& slab, int ns) {
+  TORCH_CHECK(is_nhwc_rows(x), "bn dx-only: x must be channels_last");
+  join_check(x, g, "g");
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16, "bn dx-only: bf16 only");
+  TORCH_CHECK(slab.is_cuda() && slab.scalar_type() == torch::kFloat &&
+                  slab.dim() == 2 && slab.is_contiguous() &&
+                  slab.size(0) >= 1 && slab.size(1) == ns * x.size(1),
+              "bn dx-only: slab must be fp32 [n_parts, ", ns, "*C]");
+}
+
+}  // namespace dla
+
+// The fixed-order column sum of a [n_parts, n_cols] fp32 slab on its own
+// (what the dx-only entries run first), for tests and timing.
+torch::Tensor bn_slab_reduce(torch::Tensor slab) {
+  TORCH_CHECK(slab.is_cuda() && slab.scalar_type() == torch::kFloat &&
+                  slab.dim() == 2 && slab.is_contiguous() && slab.size(0) >= 1,
+              "bn_slab_reduce: slab must be a contiguous fp32 [n_parts, n_cols] "
+              "GPU tensor");
+  auto sums = dla::bn_slab_reduce_launch(slab);
+  HIP_CHECK_ERR();
+  return sums;
+}
+
+// Returns {dx, dweight, dbias}.
+std::vector<torch::Tensor> bn_bwd_dx_from_slab(torch::Tensor g,
+                                               torch::Tensor slab,
+                                               torch::Tensor x,
+                                               torch::Tensor weight,
+                                               torch::Tensor mean,
+                                               torch::Tensor rstd) {
+  DLA_CHECK_CUDA(x);
+  dla::dx_only_check(x, g, slab, 2);
+  const int V = dla::join_vec(x);
+  const int C = (int)x.size(1);
+  const int64_t rows = x.numel() / C;
+  TORCH_CHECK(mean.numel() == C && rstd.numel() == C && weight.numel() == C,
+              "bn_bwd_dx_from_slab: per-channel tensors must have C elements");
+  auto dx = torch::empty_like(x);
+  auto w32 = weight.to(torch::kFloat).contiguous();
+  auto sums = dla::bn_slab_reduce_launch(slab);
+  using dev_t = __hip_bfloat16;
+  const int64_t used = dla::nhwc_used_threads(C / V, rows, 524288);
+  hipLaunchKernelGGL((dla::bn_bwd_dx_nhwc_kernel<dev_t, 8, false>),
+                     dim3((int)((used + 255) / 256)), dim3(256), 0,
+                     dla::stream(), (const dev_t*)g.data_ptr(),
+                     (const dev_t*)x.data_ptr(), nullptr, nullptr, nullptr,
+                     mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                     w32.data_ptr<float>(), sums.data_ptr<float>(),
+                     (dev_t*)dx.data_ptr(), C, rows, used, 1.f / (float)rows);
+  HIP_CHECK_ERR();
+  return {dx, dla::bn_param_grad(sums, C, C, weight),
+          dla::bn_param_grad(sums, 0, C, weight)};
+}
+
+// Dual join. Returns {dx, dxd, dweight, dbias, dweight_d, dbias_d}.
+std::vector<torch::Tensor> bn_join_dual_bwd_dx_from_slab(
+    torch::Tensor g, torch::Tensor slab, torch::Tensor x, torch::Tensor weight,
+    torch::Tensor mean, torch::Tensor rstd, torch::Tensor xd,
+    torch::Tensor weight_d, torch::Tensor mean_d, torch::Tensor rstd_d) {
+  DLA_CHECK_CUDA(x);
+  dla::dx_only_check(x, g, slab, 3);
+  dla::join_check(x, xd, "xd");
+  const int V = dla::join_vec(x);
+  const int C = (int)x.size(1);
+  const int64_t rows = x.numel() / C;
+  TORCH_CHECK(mean.numel() == C && rstd.numel() == C && weight.numel() == C &&
+                  mean_d.numel() == C && rstd_d.numel() == C &&
+                  weight_d.numel() == C,
+              "bn_join_dual_bwd_dx_from_slab: per-channel tensors must have C "
+              "elements");
+  auto dx = torch::empty_like(x);
+  auto dxd = torch::empty_like(x);
+  auto w32 = weight.to(torch::kFloat).contiguous();
+  auto wd32 = weight_d.to(torch::kFloat).contiguous();
+  auto sums = dla::bn_slab_reduce_launch(slab);
+  using dev_t = __hip_bfloat16;
+  const int64_t used = dla::nhwc_used_threads(C / V, rows, 524288);
+  hipLaunchKernelGGL((dla::bn_join_bwd_dx_dual_nhwc_kernel<dev_t, 8>),
+                     dim3((int)((used + 255) / 256)), dim3(256), 0,
+                     dla::stream(), (const dev_t*)g.data_ptr(),
+                     (const dev_t*)x.data_ptr(), (const dev_t*)xd.data_ptr(),
+                     mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                     w32.data_ptr<float>(), mean_d.data_ptr<float>(),
+                     rstd_d.data_ptr<float>(), wd32.data_ptr<float>(),
+                     sums.data_ptr<float>(), (dev_t*)dx.data_ptr(),
+                     (dev_t*)dxd.data_ptr(), C, rows, used,
+                     1.f / (float)rows);
+  HIP_CHECK_ERR();
   auto dbias = dla::bn_param_grad(sums, 0, C, weight);
   return {dx, dxd, dla::bn_param_grad(sums, C, C, weight), dbias,
           dla::bn_param_grad(sums, 2 * C, C, weight_d),

@@ -66,7 +66,24 @@ std::vector<torch::Tensor> bn_add_relu_dual_bwd(
     torch::Tensor dy, torch::Tensor out, torch::Tensor x, torch::Tensor weight,
     torch::Tensor mean, torch::Tensor rstd, torch::Tensor xd,
     torch::Tensor weight_d, torch::Tensor mean_d, torch::Tensor rstd_d);
+torch::Tensor bn_slab_reduce(torch::Tensor slab);
+std::vector<torch::Tensor> bn_bwd_dx_from_slab(torch::Tensor g,
+                                               torch::Tensor slab,
+                                               torch::Tensor x,
+                                               torch::Tensor weight,
+                                               torch::Tensor mean,
+                                               torch::Tensor rstd);
+std::vector<torch::Tensor> bn_join_dual_bwd_dx_from_slab(
+    torch::Tensor g, torch::Tensor slab, torch::Tensor x, torch::Tensor weight,
+    torch::Tensor mean, torch::Tensor rstd, torch::Tensor xd,
+    torch::Tensor weight_d, torch::Tensor mean_d, torch::Tensor rstd_d);
 // conv1x1.hip
+std::vector<torch::Tensor> conv1x1_dgrad_bwdstats(
+    torch::Tensor dy, torch::Tensor wt, c10::optional<torch::Tensor> residual,
+    int64_t mode, c10::optional<torch::Tensor> out, torch::Tensor x,
+    c10::optional<torch::Tensor> scale, c10::optional<torch::Tensor> shift,
+    torch::Tensor mean, torch::Tensor rstd, c10::optional<torch::Tensor> xd,
+    c10::optional<torch::Tensor> mean_d, c10::optional<torch::Tensor> rstd_d);
 std::vector<torch::Tensor> conv1x1_fwd(torch::Tensor a, torch::Tensor b,
                                        c10::optional<torch::Tensor> bias,
                                        c10::optional<torch::Tensor> scale,
@@ -176,6 +193,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bias") = py::none(), py::arg("scale") = py::none(),
         py::arg("shift") = py::none(), py::arg("residual") = py::none(),
         py::arg("relu") = false, py::arg("want_stats") = false);
+  m.def("conv1x1_dgrad_bwdstats", &conv1x1_dgrad_bwdstats, py::arg("dy"),
+        py::arg("wt"), py::arg("residual"), py::arg("mode"), py::arg("out"),
+        py::arg("x"), py::arg("scale"), py::arg("shift"), py::arg("mean"),
+        py::arg("rstd"), py::arg("xd") = py::none(),
+        py::arg("mean_d") = py::none(), py::arg("rstd_d") = py::none());
+  m.def("bn_slab_reduce", &bn_slab_reduce);
+  m.def("bn_bwd_dx_from_slab", &bn_bwd_dx_from_slab);
+  m.def("bn_join_dual_bwd_dx_from_slab", &bn_join_dual_bwd_dx_from_slab);
   m.def("conv1x1_wgrad", &conv1x1_wgrad);
   m.def("conv3x3_fwd", &conv3x3_fwd, py::arg("a"), py::arg("w9"),
         py::arg("imgH"), py::arg("imgW"), py::arg("bias") = py::none(),

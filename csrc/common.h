@@ -64,6 +64,21 @@ template <typename scalar_t> struct DevT { using type = scalar_t; };
 template <> struct DevT<at::BFloat16> { using type = __hip_bfloat16; };
 template <> struct DevT<at::Half> { using type = __half; };
 
+// The BN pre-activation x*scale + shift as ONE explicit fused multiply-add.
+// The forward apply kernels and the ReLU mask of the backward kernels both go
+// through this function, so the mask `bn_pre(x, sc, sh) > 0` is decided by the
+// very instruction sequence that produced y.
+//
+// Known edge of masking from x and not from the stored y: the two differ
+// only where a positive fp32 pre-activation rounds to zero in the storage
+// type. bf16 has fp32's exponent range, so that needs a value below bf16's
+// smallest subnormal (~9e-41); for fp16 it is anything below ~3e-8. A NaN
+// pre-activation gives mask 0 on both routes (fmaxf(NaN, 0) = 0 forward,
+// NaN > 0 false backward).
+__device__ __forceinline__ float bn_pre(float x, float sc, float sh) {
+  return fmaf(x, sc, sh);
+}
+
 // ---- wave & block reductions -------------------------------------------------
 __device__ __forceinline__ float wave_reduce_sum(float v) {
 #pragma unroll

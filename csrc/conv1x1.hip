@@ -54,15 +54,54 @@ __device__ __forceinline__ void glds16(const bf16* gsrc, bf16* lds_dst) {
 // input row with zero predication at the image boundary; everything else
 // (B staging from the wrapper-pre-permuted [Co][9Ci] weight, MFMA loop,
 // stats/bias/scale/relu/residual epilogue, store transpose) is shared.
-template <int BN, bool STATS, int BK = 64, int TAPS = 1, int RING = 0>
-__global__ __launch_bounds__((BN == 256) ? 512 : 256) void conv1x1_nt_kernel(
+//
+// BWD != BWD_NONE (dgrad only): the store pass also does pass 1 of the BN
+// backward whose output gradient this GEMM produces. v is the bf16 value the
+// plain kernel would store (after the residual add and its rounding):
+//   BWD_RELU_X     g = bn_pre(x, scale, shift) > 0 ? v : 0   (BN + ReLU)
+//   BWD_JOIN       g = out > 0 ? v : 0                       (residual join)
+//   BWD_JOIN_DUAL  as JOIN, with the second BN's x-hat
+// g is stored in place of v, and sum g, sum g*xhat (DUAL: sum g*xhat_d) of
+// the block's rows go to row blockIdx.y of a [gridDim.y, NS*N] slab, layout
+// {sum g [N], sum g*xhat [N], (DUAL) sum g*xhat_d [N]} as the BN reduction
+// kernels write it. Every (m-block, n-block) stores its [NS*BN] slice once:
+// no atomics, no zero fill, fixed summation order.
+enum BwdMode { BWD_NONE = 0, BWD_RELU_X = 1, BWD_JOIN = 2, BWD_JOIN_DUAL = 3 };
+
+struct BwdEpi {
+  const bf16* out;      // [M,N] join output (JOIN, JOIN_DUAL)
+  const bf16* x;        // [M,N] raw input of the BN
+  const bf16* xd;       // [M,N] raw input of the second BN (JOIN_DUAL)
+  const float* scale;   // [N] forward scale / shift of the BN (RELU_X)
+  const float* shift;
+  const float* mean;    // [N]
+  const float* rstd;
+  const float* mean_d;  // [N] (JOIN_DUAL)
+  const float* rstd_d;
+  float* slab;          // [gridDim.y, NS*N]
+};
+
+template <int BN, bool STATS, int BK = 64, int TAPS = 1, int RING = 0,
+          int BWD = BWD_NONE>
+// The backward-stats modes ask for the 3 waves per SIMD the plain BN=128
+// dgrad runs at: left alone, their extra epilogue state costs a block per CU
+// (the allocator then spends the accumulator registers as well: 138-168
+// unified, no spill). BWD_NONE asks for nothing (1 is the default minimum).
+// They are built for BN 64 and 128 only: the 8-wave BN=256 variant has 128
+// registers per lane, spilled and measured slower than the separate pass.
+__global__ __launch_bounds__((BN == 256) ? 512 : 256)
+__attribute__((amdgpu_waves_per_eu(BWD == BWD_NONE ? 1 : 3))) void
+conv1x1_nt_kernel(
     const bf16* __restrict__ A, const bf16* __restrict__ B,
     bf16* __restrict__ C, const bf16* __restrict__ residual,  // [M,N] | null
     const float* __restrict__ bias,                           // [N] | null
     const float* __restrict__ scale,                          // [N] | null
     const float* __restrict__ shift,                          // [N] | null
     float* __restrict__ sums,  // [gridDim.x, 2N] per-block partials | null
-    int64_t M, int K, int N, bool relu, int imgH = 0, int imgW = 0) {
+    int64_t M, int K, int N, bool relu, int imgH = 0, int imgW = 0,
+    BwdEpi be = BwdEpi{}) {
+  static_assert(BWD == BWD_NONE || (!STATS && TAPS == 1 && BN != 256),
+                "the backward-stats epilogue belongs to the 1x1 dgrad");
   constexpr int BM = 128;
   constexpr int NWAVES = (BN == 256) ? 8 : 4;
   constexpr int WAVES_M = (BN == 64) ? 4 : 2;
@@ -309,6 +348,27 @@ __global__ __launch_bounds__((BN == 256) ? 512 : 256) void conv1x1_nt_kernel(
   for (int ni = 0; ni < NFR; ++ni)
     bcol[ni] = bias != nullptr ? bias[n0 + wn_off + ni * 16 + (lane & 15)]
                                : 0.f;
+  // backward-stats state: this lane's 8 channels, summed over its rows
+  constexpr bool BDUAL = BWD == BWD_JOIN_DUAL;
+  constexpr int BNS = BWD == BWD_NONE ? 1 : (BDUAL ? 3 : 2);
+  float bacc[BNS][8], bmu[8], brs[8], bmud[8], brsd[8], bsc[8], bsh[8];
+  if constexpr (BWD != BWD_NONE) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      bmu[j] = be.mean[ng0 + j];
+      brs[j] = be.rstd[ng0 + j];
+      if constexpr (BDUAL) {
+        bmud[j] = be.mean_d[ng0 + j];
+        brsd[j] = be.rstd_d[ng0 + j];
+      }
+      if constexpr (BWD == BWD_RELU_X) {
+        bsc[j] = be.scale[ng0 + j];
+        bsh[j] = be.shift[ng0 + j];
+      }
+#pragma unroll
+      for (int s = 0; s < BNS; ++s) bacc[s][j] = 0.f;
+    }
+  }
 #pragma unroll
   for (int h = 0; h < EPC; ++h) {
 #pragma unroll
@@ -333,6 +393,12 @@ __global__ __launch_bounds__((BN == 256) ? 512 : 256) void conv1x1_nt_kernel(
         Vec<bf16, 8> res;
         if (residual != nullptr)
           res = vload<bf16, 8>(residual + gm * N + ng0);
+        Vec<bf16, 8> bo, bx, bxd;  // mask source and x-hat inputs
+        if constexpr (BWD == BWD_JOIN || BDUAL)
+          bo = vload<bf16, 8>(be.out + gm * N + ng0);
+        if constexpr (BWD != BWD_NONE)
+          bx = vload<bf16, 8>(be.x + gm * N + ng0);
+        if constexpr (BDUAL) bxd = vload<bf16, 8>(be.xd + gm * N + ng0);
         Vec<bf16, 8> out;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -341,11 +407,59 @@ __global__ __launch_bounds__((BN == 256) ? 512 : 256) void conv1x1_nt_kernel(
           if (residual != nullptr) y += to_f32(res.v[j]);
           if (relu) y = fmaxf(y, 0.f);
           out.v[j] = from_f32<bf16>(y);
+          if constexpr (BWD != BWD_NONE) {
+            // mask and sum the rounded value, as the separate pass 1 does
+            const float xf = to_f32(bx.v[j]);
+            const bool on = BWD == BWD_RELU_X
+                                ? bn_pre(xf, bsc[j], bsh[j]) > 0.f
+                                : to_f32(bo.v[j]) > 0.f;
+            if (!on) out.v[j] = from_f32<bf16>(0.f);
+            const float g = on ? to_f32(out.v[j]) : 0.f;
+            bacc[0][j] += g;
+            bacc[1][j] += g * ((xf - bmu[j]) * brs[j]);
+            if constexpr (BDUAL)
+              bacc[2][j] += g * ((to_f32(bxd.v[j]) - bmud[j]) * brsd[j]);
+          }
         }
         vstore<bf16, 8>(C + gm * N + ng0, out);
       }
     }
     if (h + 1 < EPC) __syncthreads();
+  }
+
+  if constexpr (BWD != BWD_NONE) {
+    // lanes l, l^8, l^16, l^32 hold the same 8 channels (different rows):
+    // fixed xor order, then the WAVES_M waves of a column through LDS in
+    // ascending order, as the forward STATS epilogue does
+#pragma unroll
+    for (int s = 0; s < BNS; ++s)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float t = bacc[s][j];
+        t += __shfl_xor(t, 8, 64);
+        t += __shfl_xor(t, 16, 64);
+        t += __shfl_xor(t, 32, 64);
+        bacc[s][j] = t;
+      }
+    __syncthreads();  // every wave is done with its transpose scratch
+    float* sbuf = (float*)lds_raw;  // [WAVES_M][BNS * BN]
+    const int wm = wave / WAVES_N;
+    if (lane < 8) {
+#pragma unroll
+      for (int s = 0; s < BNS; ++s)
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          sbuf[wm * (BNS * BN) + s * BN + wn_off + c0 + j] = bacc[s][j];
+    }
+    __syncthreads();
+    float* row = be.slab + (int64_t)blockIdx.y * (BNS * N);  // m-block row
+    for (int t = threadIdx.x; t < BNS * BN; t += NWAVES * 64) {
+      float tot = 0.f;
+#pragma unroll
+      for (int wmi = 0; wmi < WAVES_M; ++wmi)
+        tot += sbuf[wmi * (BNS * BN) + t];
+      row[(t / BN) * N + n0 + (t % BN)] = tot;
+    }
   }
 }
 
@@ -722,13 +836,14 @@ __global__ __launch_bounds__(256) void wgrad_finalize_kernel(
 }  // namespace dla
 
 // A [M,K] bf16, B [N,K] bf16 -> C = A @ B^T [M,N] bf16, with fused epilogue.
-// Returns {C, sums[2N] fp32} (sums undefined unless want_stats).
-std::vector<torch::Tensor> conv1x1_fwd(torch::Tensor a, torch::Tensor b,
-                                       c10::optional<torch::Tensor> bias,
-                                       c10::optional<torch::Tensor> scale,
-                                       c10::optional<torch::Tensor> shift,
-                                       c10::optional<torch::Tensor> residual,
-                                       bool relu, bool want_stats) {
+// Returns {C, sums}: the [gx, 2N] forward stats slab with want_stats, the
+// [gx, NS*N] backward-stats slab with bwd != BWD_NONE (be.slab is set here),
+// else empty. Tile selection is the same for every mode.
+static std::vector<torch::Tensor> conv1x1_run(
+    torch::Tensor a, torch::Tensor b, c10::optional<torch::Tensor> bias,
+    c10::optional<torch::Tensor> scale, c10::optional<torch::Tensor> shift,
+    c10::optional<torch::Tensor> residual, bool relu, bool want_stats,
+    int bwd, dla::BwdEpi be) {
   DLA_CHECK_INPUT(a);
   DLA_CHECK_INPUT(b);
   TORCH_CHECK(a.scalar_type() == torch::kBFloat16 &&
@@ -738,6 +853,8 @@ std::vector<torch::Tensor> conv1x1_fwd(torch::Tensor a, torch::Tensor b,
   const int K = (int)a.size(1), N = (int)b.size(0);
   TORCH_CHECK((int)b.size(1) == K, "conv1x1_fwd: K mismatch");
   TORCH_CHECK(K % 64 == 0 && N % 64 == 0, "conv1x1_fwd: K,N must be %64");
+  TORCH_CHECK(bwd == dla::BWD_NONE || !want_stats,
+              "conv1x1: forward and backward stats do not combine");
   auto C = torch::empty({M, N}, a.options());
   auto opts_f = a.options().dtype(torch::kFloat);
   const int gx = (int)((M + 127) / 128);
@@ -745,6 +862,10 @@ std::vector<torch::Tensor> conv1x1_fwd(torch::Tensor a, torch::Tensor b,
   // by the caller with one torch sum — no global atomics)
   auto sums = want_stats ? torch::empty({gx, 2 * N}, opts_f)
                          : torch::empty({0}, opts_f);
+  if (bwd != dla::BWD_NONE) {
+    sums = torch::empty({gx, (bwd == dla::BWD_JOIN_DUAL ? 3 : 2) * N}, opts_f);
+    be.slab = sums.data_ptr<float>();
+  }
   const dla::bf16* res_p =
       residual.has_value() ? (const dla::bf16*)residual->data_ptr() : nullptr;
   const float* bias_p = bias.has_value() ? bias->data_ptr<float>() : nullptr;
@@ -753,10 +874,11 @@ std::vector<torch::Tensor> conv1x1_fwd(torch::Tensor a, torch::Tensor b,
   float* sums_p = want_stats ? sums.data_ptr<float>() : nullptr;
 
   const int nk = K / 64;
-  auto launch = [&](auto bntag, auto stag, auto bktag) {
+  auto launch_mode = [&](auto bntag, auto stag, auto bktag, auto modetag) {
     constexpr int BN = decltype(bntag)::value;
     constexpr bool ST = decltype(stag)::value;
     constexpr int BKT = decltype(bktag)::value;
+    constexpr int MODE = decltype(modetag)::value;
     constexpr int NW = (BN == 256) ? 8 : 4;
     constexpr int WM = (BN == 64) ? 32 : 64;
     // single staging buffer suffices when there is only one K-step; with one
@@ -771,17 +893,41 @@ std::vector<torch::Tensor> conv1x1_fwd(torch::Tensor a, torch::Tensor b,
       static bool done[2] = {false, false};
       if (!done[ST]) {
         (void)hipFuncSetAttribute(
-            (const void*)&dla::conv1x1_nt_kernel<BN, ST, BKT>,
+            (const void*)&dla::conv1x1_nt_kernel<BN, ST, BKT, 1, 0, MODE>,
             hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
         done[ST] = true;
       }
     }
-    hipLaunchKernelGGL((dla::conv1x1_nt_kernel<BN, ST, BKT>), dim3(N / BN, gx),
-                       dim3(NW * 64), lds, dla::stream(),
+    hipLaunchKernelGGL((dla::conv1x1_nt_kernel<BN, ST, BKT, 1, 0, MODE>),
+                       dim3(N / BN, gx), dim3(NW * 64), lds, dla::stream(),
                        (const dla::bf16*)a.data_ptr(),
                        (const dla::bf16*)b.data_ptr(),
                        (dla::bf16*)C.data_ptr(), res_p, bias_p, scale_p,
-                       shift_p, sums_p, M, K, N, relu);
+                       shift_p, sums_p, M, K, N, relu, 0, 0, be);
+  };
+  auto launch = [&](auto bntag, auto stag, auto bktag) {
+    using std::integral_constant;
+    if constexpr (decltype(stag)::value || decltype(bntag)::value == 256) {
+      launch_mode(bntag, stag, bktag, integral_constant<int, dla::BWD_NONE>{});
+    } else {
+      switch (bwd) {
+        case dla::BWD_RELU_X:
+          launch_mode(bntag, stag, bktag,
+                      integral_constant<int, dla::BWD_RELU_X>{});
+          break;
+        case dla::BWD_JOIN:
+          launch_mode(bntag, stag, bktag,
+                      integral_constant<int, dla::BWD_JOIN>{});
+          break;
+        case dla::BWD_JOIN_DUAL:
+          launch_mode(bntag, stag, bktag,
+                      integral_constant<int, dla::BWD_JOIN_DUAL>{});
+          break;
+        default:
+          launch_mode(bntag, stag, bktag,
+                      integral_constant<int, dla::BWD_NONE>{});
+      }
+    }
   };
   // BK=32 halves the staging LDS (4 blocks/CU): measured +5% at K=128
   // (nk==2, the exposed-drain case), neutral/negative deeper — default it
@@ -809,7 +955,8 @@ std::vector<torch::Tensor> conv1x1_fwd(torch::Tensor a, torch::Tensor b,
   };
   auto pick = [&](auto bntag) {
     constexpr int BNv = decltype(bntag)::value;
-    if (BNv == 128 && ring_on && K % 32 == 0 && K / 32 >= 4) {
+    if (BNv == 128 && ring_on && bwd == dla::BWD_NONE && K % 32 == 0 &&
+        K / 32 >= 4) {
       if (want_stats) launch_ring(std::true_type{});
       else launch_ring(std::false_type{});
       return;
@@ -827,11 +974,87 @@ std::vector<torch::Tensor> conv1x1_fwd(torch::Tensor a, torch::Tensor b,
   // BN=256 (512 threads, single A pass) wins only at nk==1 where the LDS
   // fits 3 blocks/CU; at nk>=2 its 96KB double-buffer drops occupancy to
   // 1 block/CU and BN=128 (2 blocks/CU) measures faster.
-  if (N % 256 == 0 && nk == 1) pick(std::integral_constant<int, 256>{});
+  // The backward-stats modes take BN=128 there: 0.35 ms at 802816x64x256
+  // (the byte floor) against 0.51 ms for a BN=256 variant
+  // (profiles/bwdstats_epilogue_ab.txt).
+  if (N % 256 == 0 && nk == 1 && bwd == dla::BWD_NONE)
+    pick(std::integral_constant<int, 256>{});
   else if (N % 128 == 0) pick(std::integral_constant<int, 128>{});
   else pick(std::integral_constant<int, 64>{});
   HIP_CHECK_ERR();
   return {C, sums};
+}
+
+std::vector<torch::Tensor> conv1x1_fwd(torch::Tensor a, torch::Tensor b,
+                                       c10::optional<torch::Tensor> bias,
+                                       c10::optional<torch::Tensor> scale,
+                                       c10::optional<torch::Tensor> shift,
+                                       c10::optional<torch::Tensor> residual,
+                                       bool relu, bool want_stats) {
+  return conv1x1_run(a, b, bias, scale, shift, residual, relu, want_stats,
+                     dla::BWD_NONE, dla::BwdEpi{});
+}
+
+// dgrad with the backward-stats epilogue: dy [M,K] bf16, wt [N,K] bf16 (the
+// transposed weight), optional residual [M,N] (the identity gradient).
+//   mode 1 (RELU_X):    x, scale, shift, mean, rstd
+//   mode 2 (JOIN):      out, x, mean, rstd
+//   mode 3 (JOIN_DUAL): out, x, mean, rstd, xd, mean_d, rstd_d
+// out / x / xd are [M,N] bf16 rows (NHWC tensors pass as they are), the
+// per-channel tensors fp32 [N]. Returns {g [M,N] bf16, slab [ceil(M/128),
+// NS*N] fp32}; g is the masked dgrad output, bit for bit what pass 1 of the
+// BN backward would write from the plain dgrad output.
+std::vector<torch::Tensor> conv1x1_dgrad_bwdstats(
+    torch::Tensor dy, torch::Tensor wt, c10::optional<torch::Tensor> residual,
+    int64_t mode, c10::optional<torch::Tensor> out, torch::Tensor x,
+    c10::optional<torch::Tensor> scale, c10::optional<torch::Tensor> shift,
+    torch::Tensor mean, torch::Tensor rstd, c10::optional<torch::Tensor> xd,
+    c10::optional<torch::Tensor> mean_d, c10::optional<torch::Tensor> rstd_d) {
+  TORCH_CHECK(mode >= dla::BWD_RELU_X && mode <= dla::BWD_JOIN_DUAL,
+              "conv1x1_dgrad_bwdstats: mode must be 1, 2 or 3");
+  const int64_t M = dy.size(0), N = wt.size(0);
+  auto rows_ok = [&](const torch::Tensor& t) {
+    return t.is_cuda() && t.scalar_type() == torch::kBFloat16 &&
+           t.numel() == M * N &&
+           (t.dim() == 2 ? t.is_contiguous() && t.size(1) == N
+                         : t.dim() == 4 && t.size(1) == N &&
+                               t.is_contiguous(at::MemoryFormat::ChannelsLast));
+  };
+  auto chan_ok = [&](const torch::Tensor& t) {
+    return t.is_cuda() && t.scalar_type() == torch::kFloat &&
+           t.is_contiguous() && t.numel() == N;
+  };
+  TORCH_CHECK(rows_ok(x), "conv1x1_dgrad_bwdstats: x must be [M,N] bf16 rows");
+  TORCH_CHECK(chan_ok(mean) && chan_ok(rstd),
+              "conv1x1_dgrad_bwdstats: mean/rstd must be fp32 [N]");
+  TORCH_CHECK(!residual.has_value() ||
+                  (rows_ok(*residual) && residual->dim() == 2),
+              "conv1x1_dgrad_bwdstats: residual must be [M,N] bf16");
+  dla::BwdEpi be{};
+  be.x = (const dla::bf16*)x.data_ptr();
+  be.mean = mean.data_ptr<float>();
+  be.rstd = rstd.data_ptr<float>();
+  if (mode == dla::BWD_RELU_X) {
+    TORCH_CHECK(scale.has_value() && shift.has_value() && chan_ok(*scale) &&
+                    chan_ok(*shift),
+                "conv1x1_dgrad_bwdstats: RELU_X needs fp32 [N] scale/shift");
+    be.scale = scale->data_ptr<float>();
+    be.shift = shift->data_ptr<float>();
+  } else {
+    TORCH_CHECK(out.has_value() && rows_ok(*out),
+                "conv1x1_dgrad_bwdstats: JOIN needs out as [M,N] bf16 rows");
+    be.out = (const dla::bf16*)out->data_ptr();
+  }
+  if (mode == dla::BWD_JOIN_DUAL) {
+    TORCH_CHECK(xd.has_value() && rows_ok(*xd) && mean_d.has_value() &&
+                    rstd_d.has_value() && chan_ok(*mean_d) && chan_ok(*rstd_d),
+                "conv1x1_dgrad_bwdstats: JOIN_DUAL needs xd, mean_d, rstd_d");
+    be.xd = (const dla::bf16*)xd->data_ptr();
+    be.mean_d = mean_d->data_ptr<float>();
+    be.rstd_d = rstd_d->data_ptr<float>();
+  }
+  return conv1x1_run(dy, wt, c10::nullopt, c10::nullopt, c10::nullopt,
+                     residual, false, false, (int)mode, be);
 }
 
 // 3x3 stride-1 pad-1 conv as tap-major implicit GEMM (TAPS=9 variant of

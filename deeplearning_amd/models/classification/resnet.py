@@ -9,7 +9,10 @@ epilogue (csrc/conv1x1.hip); 3x3 convs run MIOpen by default with a fully
 hand-written TAPS=9 route available (DLA_CONV3X3=1, see ROADMAP); each
 Bottleneck join is one kernel that applies bn3 (and the downsample bn), adds
 the identity and applies ReLU (DLA_NO_FUSED_JOIN=1 restores bn apply +
-add_relu); BasicBlock joins are one fused add+relu kernel. In train mode the
+add_relu), and where a join feeds the next block's pass-through conv1, pass 1
+of its backward runs in that conv's dgrad epilogue
+(DLA_NO_BWD_STATS_EPILOGUE=1 restores the separate pass); BasicBlock joins are
+one fused add+relu kernel. In train mode the
 stem's bn1 + ReLU + 3x3/s2 max-pool is one apply+pool kernel that never writes
 the BN output and keeps a uint8 window slot in place of int64 indices, with a
 two-pass gather backward (DLA_NO_FUSED_STEM=1 restores bn1 then nn.MaxPool2d);

@@ -20,7 +20,10 @@ import torch.nn.functional as F
 from torch import nn
 
 from ._ext import ext, use_hip
-from .batchnorm import bn_backward, save_bn_for_backward
+from .batchnorm import (JOIN, JOIN_DUAL, RELU_X, BwdStatsLink,
+                        attach_relu_link, bn_backward,
+                        bwd_stats_epilogue_disabled, link_eligible,
+                        save_bn_for_backward)
 
 
 def _flatten_nhwc(x: torch.Tensor) -> torch.Tensor:
@@ -47,12 +50,20 @@ class _Conv1x1Fn(torch.autograd.Function):
     gradient to THIS node, which folds it into the dgrad GEMM's residual
     epilogue (dx = dy @ W + d_alias in the store pass) — autograd no longer
     sums the block input's two gradients with a separate add kernel.
+
+    link: the BwdStatsLink of the BN or join that produced x2d. The dgrad
+    GEMM then also runs pass 1 of that producer's backward in its store pass
+    (mask, store g, partial sums) and hands g and the slab over through the
+    link; g is a valid gradient for x2d either way, because masking twice is
+    masking once.
     """
 
     @staticmethod
     def forward(ctx, x2d, w, bias, scale, shift, residual, relu, want_stats,
-                pass_input=False):
+                pass_input=False, link=None):
         xb = x2d if x2d.dtype == torch.bfloat16 else x2d.to(torch.bfloat16)
+        # the join modes mask from xb, which must be the producer's output
+        ctx.link = link if xb is x2d else None
         wb = w if w.dtype == torch.bfloat16 else w.to(torch.bfloat16)
         wb = wb.contiguous()
         y2d, sums = ext().conv1x1_fwd(xb, wb, bias, scale, shift, residual,
@@ -81,7 +92,7 @@ class _Conv1x1Fn(torch.autograd.Function):
         if dy2d is None:  # only the pass-through output was used
             if d_alias is not None and ctx.needs_input_grad[0]:
                 dx = d_alias.to(ctx.x_dtype)
-            return dx, None, None, None, None, None, None, None, None
+            return dx, None, None, None, None, None, None, None, None, None
         dy2d = dy2d.contiguous()
         if dy2d.dtype != torch.bfloat16:
             dy2d = dy2d.to(torch.bfloat16)
@@ -90,8 +101,20 @@ class _Conv1x1Fn(torch.autograd.Function):
             wt = ext().transpose2d(wb)  # [K,N] bf16
             if d_alias is not None and d_alias.dtype != torch.bfloat16:
                 d_alias = d_alias.to(torch.bfloat16)
-            dx, _ = ext().conv1x1_fwd(dy2d, wt, None, None, None, d_alias,
-                                      False, False)
+            link = ctx.link
+            ops = link.take_operands() if link is not None else None
+            if ops is not None and ops["x_raw"].numel() == xb.numel() and \
+                    ops["x_raw"].shape[1] == xb.shape[1]:
+                dx, slab = ext().conv1x1_dgrad_bwdstats(
+                    dy2d, wt, d_alias, link.mode,
+                    None if link.mode == RELU_X else xb, ops["x_raw"],
+                    ops.get("scale"), ops.get("shift"), ops["mean"],
+                    ops["rstd"], ops.get("xd_raw"), ops.get("mean_d"),
+                    ops.get("rstd_d"))
+                link.offer(dx, slab)
+            else:
+                dx, _ = ext().conv1x1_fwd(dy2d, wt, None, None, None,
+                                          d_alias, False, False)
             if dx.dtype != ctx.x_dtype:
                 dx = dx.to(ctx.x_dtype)
         if ctx.needs_input_grad[1]:
@@ -102,7 +125,7 @@ class _Conv1x1Fn(torch.autograd.Function):
             # bias rides the fused epilogue in forward; its grad is the
             # per-channel column sum of dy
             db = dy2d.float().sum(0)
-        return dx, dw, db, None, None, None, None, None, None
+        return dx, dw, db, None, None, None, None, None, None, None
 
 
 class _BNFromStatsFn(torch.autograd.Function):
@@ -197,13 +220,22 @@ def _conv1x1_train_stats(x: torch.Tensor, conv: nn.Conv2d, bn,
     """Train-mode front half shared by conv1x1_bn and the fused join: conv
     GEMM with the stats epilogue plus the BN bookkeeping. Returns (raw conv
     output NHWC 4D, [n_blocks, 2C] stats partials, momentum, x alias|None)."""
+    # the backward-stats link of x's producer, if this conv may serve it: x
+    # itself is the GEMM operand (stride 1, bf16), and a join's output has no
+    # other consumer than this conv and the identity that rides its dgrad
+    link = getattr(x, "_dla_bwd_link", None)
+    if link is not None and (
+            bwd_stats_epilogue_disabled() or conv.stride != (1, 1) or
+            x.dtype != torch.bfloat16 or
+            (link.mode != RELU_X and not pass_input)):
+        link = None
     x2d, wb, bias, (B, H, W) = _prep(x, conv)
     _fp32_running_stats(bn)
     if bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
     momentum = bn._eaf() if hasattr(bn, "_eaf") else (bn.momentum or 0.0)
     outs = _Conv1x1Fn.apply(x2d, wb, bias, None, None, None, False, True,
-                            pass_input)
+                            pass_input, link)
     alias = _unflatten_nhwc(outs[2], B, H, W) if pass_input else None
     return _unflatten_nhwc(outs[0], B, H, W), outs[1], momentum, alias
 
@@ -228,6 +260,8 @@ def conv1x1_bn(x: torch.Tensor, conv: nn.Conv2d, bn,
         y = _BNFromStatsFn.apply(y_raw, bn.weight, bn.bias, partials,
                                  bn.running_mean, bn.running_var, momentum,
                                  bn.eps, relu)
+        if relu:
+            attach_relu_link(y)
         return (y, alias) if pass_input else y
     if pass_input:
         raise ValueError("conv1x1_bn: pass_input needs train mode")
@@ -273,8 +307,15 @@ class _BNJoinFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x_raw, out, weight, mean, rstd = ctx.saved_tensors
-        g, dx, dw, db = ext().bn_add_relu_bwd(dy, out, x_raw, weight, mean,
-                                              rstd)
+        link = getattr(ctx, "link", None)
+        slab = link.claim(dy, out) if link is not None else None
+        if slab is not None:  # dy is g: the next conv1's dgrad ran pass 1
+            g = dy
+            dx, dw, db = ext().bn_bwd_dx_from_slab(g, slab, x_raw, weight,
+                                                   mean, rstd)
+        else:
+            g, dx, dw, db = ext().bn_add_relu_bwd(dy, out, x_raw, weight,
+                                                  mean, rstd)
         return dx, dw, db, None, None, None, None, None, g
 
 
@@ -299,15 +340,49 @@ class _BNJoinDualFn(torch.autograd.Function):
     def backward(ctx, dy):
         (x_raw, xd_raw, out, weight, mean, rstd, weight_d, mean_d,
          rstd_d) = ctx.saved_tensors
-        dx, dxd, dw, db, dwd, dbd = ext().bn_add_relu_dual_bwd(
-            dy, out, x_raw, weight, mean, rstd, xd_raw, weight_d, mean_d,
-            rstd_d)
+        link = getattr(ctx, "link", None)
+        slab = link.claim(dy, out) if link is not None else None
+        if slab is not None:
+            dx, dxd, dw, db, dwd, dbd = \
+                ext().bn_join_dual_bwd_dx_from_slab(
+                    dy, slab, x_raw, weight, mean, rstd, xd_raw, weight_d,
+                    mean_d, rstd_d)
+        else:
+            dx, dxd, dw, db, dwd, dbd = ext().bn_add_relu_dual_bwd(
+                dy, out, x_raw, weight, mean, rstd, xd_raw, weight_d,
+                mean_d, rstd_d)
         return (dx, dw, db, None, None, None, None, None,
                 dxd, dwd, dbd, None, None, None, None, None)
 
 
 def _fused_join_disabled() -> bool:
     return os.environ.get("DLA_NO_FUSED_JOIN", "0") == "1"  # A/B runs
+
+
+def _dual_epilogue_disabled() -> bool:
+    # the three-sum epilogue of the dual join (see docs/KERNELS.md)
+    return os.environ.get("DLA_NO_BWD_STATS_DUAL", "0") == "1"
+
+
+def _attach_join_link(out: torch.Tensor) -> torch.Tensor:
+    """Hang a JOIN / JOIN_DUAL link on a join output that autograd tracks.
+    Whether it is used is the consumer's decision (a pass_input conv1)."""
+    fn = out.grad_fn
+    if fn is None or bwd_stats_epilogue_disabled():
+        return out
+    saved = fn.saved_tensors
+    if len(saved) == 5:
+        x_raw, _, _, mean, rstd = saved
+        if link_eligible(x_raw):
+            fn.link = out._dla_bwd_link = BwdStatsLink(
+                JOIN, x_raw=x_raw, mean=mean, rstd=rstd)
+    elif not _dual_epilogue_disabled():
+        x_raw, xd_raw, _, _, mean, rstd, _, mean_d, rstd_d = saved
+        if link_eligible(x_raw):
+            fn.link = out._dla_bwd_link = BwdStatsLink(
+                JOIN_DUAL, x_raw=x_raw, mean=mean, rstd=rstd, xd_raw=xd_raw,
+                mean_d=mean_d, rstd_d=rstd_d)
+    return out
 
 
 def _join_bn_ok(conv: nn.Conv2d, bn) -> bool:
@@ -362,19 +437,19 @@ def conv_bn_add_relu(x: torch.Tensor, conv: nn.Conv2d, bn, identity=None,
         if downsample is None:
             if identity.shape != y_raw.shape:
                 raise ValueError("conv_bn_add_relu: identity shape mismatch")
-            return _BNJoinFn.apply(y_raw, bn.weight, bn.bias, partials,
-                                   bn.running_mean, bn.running_var, momentum,
-                                   bn.eps, identity)
+            return _attach_join_link(_BNJoinFn.apply(
+                y_raw, bn.weight, bn.bias, partials, bn.running_mean,
+                bn.running_var, momentum, bn.eps, identity))
         conv_d, bn_d = downsample[0], downsample[1]
         yd_raw, partials_d, momentum_d, _ = _conv1x1_train_stats(
             x_down, conv_d, bn_d)
         if yd_raw.shape != y_raw.shape:
             raise ValueError("conv_bn_add_relu: downsample shape mismatch")
-        return _BNJoinDualFn.apply(
+        return _attach_join_link(_BNJoinDualFn.apply(
             y_raw, bn.weight, bn.bias, partials, bn.running_mean,
             bn.running_var, momentum, bn.eps, yd_raw, bn_d.weight, bn_d.bias,
             partials_d, bn_d.running_mean, bn_d.running_var, momentum_d,
-            bn_d.eps)
+            bn_d.eps))
     from .activations import add_relu
 
     out = conv_bn(x, conv, bn)

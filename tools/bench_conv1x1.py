@@ -6,6 +6,8 @@ vs conv + separate BN, and CE old-vs-new launch overhead.
 Run on a GPU box:  python tools/bench_conv1x1.py [--quick]
                    python tools/bench_conv1x1.py --wgrad-ab   (wgrad only: old
                    route DLA_C1X1_WGRAD_V1=1 against new, with the byte floor)
+                   python tools/bench_conv1x1.py --bwdstats-ab   (dgrad with
+                   the BN backward-stats epilogue against the separate pass 1)
 """
 import argparse
 import os
@@ -76,15 +78,115 @@ def wgrad_ab(B, iters):
               f"{best['0'] / floor:9.2f}")
 
 
+def bwdstats_ab(B, iters):
+    """BN backward pass 1 in the dgrad epilogue against a pass of its own,
+    per ResNet-50 shape. relu_x: conv3 dgrad feeding bn2 (N = width); join /
+    join_dual: the next block's conv1 dgrad feeding a residual join (N = 4 *
+    width), with the identity gradient as the GEMM's residual.
+      dgrad   the plain dgrad GEMM alone
+      old     dgrad + today's two-pass BN backward entry (pass 1, slab
+              reduce, dx pass)
+      epi     the dgrad GEMM with the epilogue alone
+      red     the slab reduce alone (its slab has M/128 rows)
+      new     epi + the dx-only entry (slab reduce, dx pass)
+    old - new is what a step gains per call. floor: the unique bytes the
+    epilogue GEMM moves (A, the [M,N] reads and the g write) at FLOOR_GBPS."""
+    e = ext()
+    print(f"batch={B}  backward-stats epilogue A/B, {iters} calls per timing, "
+          "best of 3 alternating rounds, ms")
+    print(f"{'mode':>9} {'shape MxKxN':>20} {'dgrad':>7} {'old':>7} "
+          f"{'epi':>7} {'red':>7} {'new':>7} {'old-new':>8} {'epi floor':>9}")
+    widths = [(56 * 56, 64), (28 * 28, 128), (14 * 14, 256), (7 * 7, 512)]
+    for mode, name in ((1, "relu_x"), (2, "join"), (3, "join_dual")):
+        for HW, wd in widths:
+            K, N = (4 * wd, wd) if mode == 1 else (wd, 4 * wd)
+            M, H = B * HW, int(HW ** 0.5)
+
+            def nhwc(scale=1.0):
+                t = torch.randn(M, N, device="cuda") * scale
+                return t.to(torch.bfloat16).view(B, H, H, N) \
+                    .permute(0, 3, 1, 2)
+
+            x, xd, out = nhwc(), nhwc(), nhwc()
+            dy = torch.randn(M, K, device="cuda").to(torch.bfloat16)
+            wt = (torch.randn(N, K, device="cuda") / K ** 0.5) \
+                .to(torch.bfloat16)
+            res = None if mode == 1 else \
+                torch.randn(M, N, device="cuda").to(torch.bfloat16)
+            w = torch.rand(N, device="cuda") + 0.5
+            mean = torch.randn(N, device="cuda") * 0.1
+            rstd = torch.rand(N, device="cuda") + 0.5
+            scale, shift = w * rstd, -mean * w * rstd
+
+            def as4(t):
+                return t.view(B, H, H, N).permute(0, 3, 1, 2)
+
+            def dgrad():
+                return e.conv1x1_fwd(dy, wt, None, None, None, res, False,
+                                     False)[0]
+
+            def epi():
+                return e.conv1x1_dgrad_bwdstats(
+                    dy, wt, res, mode, None if mode == 1 else out, x,
+                    scale if mode == 1 else None,
+                    shift if mode == 1 else None, mean, rstd,
+                    xd if mode == 3 else None, mean if mode == 3 else None,
+                    rstd if mode == 3 else None)
+
+            def old():
+                d = as4(dgrad())
+                if mode == 1:
+                    return e.batchnorm_bwd_ex(d, x, None, w, mean, rstd,
+                                              scale, shift, True)
+                if mode == 2:
+                    return e.bn_add_relu_bwd(d, out, x, w, mean, rstd)
+                return e.bn_add_relu_dual_bwd(d, out, x, w, mean, rstd, xd,
+                                              w, mean, rstd)
+
+            def new():
+                g, slab = epi()
+                if mode == 3:
+                    return e.bn_join_dual_bwd_dx_from_slab(
+                        as4(g), slab, x, w, mean, rstd, xd, w, mean, rstd)
+                return e.bn_bwd_dx_from_slab(as4(g), slab, x, w, mean, rstd)
+
+            slab = epi()[1]
+            fns = {"dgrad": dgrad, "old": old, "epi": epi,
+                   "red": lambda: e.bn_slab_reduce(slab), "new": new}
+            best = {k: float("inf") for k in fns}
+            for _ in range(3):
+                for k, fn in fns.items():
+                    best[k] = min(best[k], timeit(fn, iters))
+            tensors = {1: 2, 2: 4, 3: 5}[mode]  # [M,N] reads + the g write
+            nbytes = 2 * M * (K + tensors * N)
+            floor = nbytes / (FLOOR_GBPS * 1e9) * 1e3
+            print(f"{name:>9} {f'{M}x{K}x{N}':>20} {best['dgrad']:7.3f} "
+                  f"{best['old']:7.3f} {best['epi']:7.3f} {best['red']:7.3f} "
+                  f"{best['new']:7.3f} {best['old'] - best['new']:8.3f} "
+                  f"{floor:9.3f}")
+    print("slab reduce alone (fixed order, two stages above 512 rows):")
+    for rows, cols in ((6272, 512), (6272, 768), (1568, 1024), (392, 2048)):
+        slab = torch.randn(rows, cols, device="cuda")
+        t = min(timeit(lambda: e.bn_slab_reduce(slab), iters)
+                for _ in range(3))
+        print(f"  {rows} x {cols}: {t * 1e3:.1f} us")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
+    ap.add_argument("--bwdstats-ab", action="store_true",
+                    help="time the dgrad backward-stats epilogue against "
+                         "the separate pass 1")
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--wgrad-ab", action="store_true",
                     help="time only wgrad, old route against new")
     args = ap.parse_args()
     if args.wgrad_ab:
         wgrad_ab(args.batch, 50 if args.quick else 200)
+        return
+    if args.bwdstats_ab:
+        bwdstats_ab(args.batch, 30 if args.quick else 100)
         return
     iters = 20 if args.quick else 50
     B = args.batch
