@@ -3,7 +3,8 @@
 // Replaces the eager softmax(Q K^T / sqrt(d) + bias + mask) V chain in
 // ViT (classification/vision_transformer/vit_model.py:88-113), Swin window
 // attention (classification/swin_transformer/models/swin_transformer.py:118-151),
-// MAE and TransFG with ONE kernel launch per tensor:
+// and MAE with ONE kernel launch per tensor (TransFG's part-selection blocks
+// need the full attention maps and keep their eager code):
 //  - consumes the packed qkv projection [B, N, 3, H, d] directly (no permute
 //    copies, no [B,H,N,N] fp32 score tensor, no separate softmax kernels);
 //  - writes O in [B, N, H*d] (the layout the output projection wants);
@@ -11,7 +12,11 @@
 //    no [B,H,N,N] tensor ever reaches HBM (optionally saves P in bf16 for
 //    the bias-gradient fallback path).
 //
-// Shape domain: d in {32, 64}, N <= 256 (ViT 197, Swin windows 49, MAE 50).
+// Shape domain: d in {32, 64}, N <= 256 (ViT 197, Swin windows 49, MAE 50);
+// the backward kernels additionally need their LDS to fit 160 KiB, which at
+// d = 64 holds for N <= 224 (attn_bwd_lds_bytes). Longer sequences, and the
+// backward of d = 64 with 225 <= N <= 256, run the streaming kernels of
+// csrc/attention_stream.hip (plain path only).
 // Design notes (rocprof-driven):
 //  - one workgroup per (b, h); 8 waves (4 for small N), each owning 16
 //    output rows at a time;
@@ -822,6 +827,19 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor qkv, int64_t num_heads,
   return res;
 }
 
+// Dynamic LDS bytes {kv kernel, q kernel} that attn_bwd launches with.
+// ops/attention._attn_route mirrors this arithmetic to keep shapes that do
+// not fit 160 KiB per CU off the resident backward.
+std::vector<int64_t> attn_bwd_lds_bytes(int64_t N, int64_t D) {
+  const int64_t Npad = (N + 15) & ~(int64_t)15;
+  const int64_t nwaves = N > 96 ? 8 : 4;
+  const int64_t lds_kv = (2 * Npad * dla::KPAD + 2 * D * (Npad + 8) +
+                          nwaves * 2 * dla::PBUF) * 2;
+  const int64_t lds_q = (2 * Npad * dla::KPAD + D * (Npad + 8) +
+                         nwaves * 2 * dla::PBUF) * 2;
+  return {lds_kv, lds_q};
+}
+
 std::vector<torch::Tensor> attn_bwd(torch::Tensor qkv, torch::Tensor dout,
                                     torch::Tensor stats, torch::Tensor drow,
                                     int64_t num_heads, double scale) {
@@ -832,13 +850,14 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor qkv, torch::Tensor dout,
   const int D = (int)(qkv.numel() / ((int64_t)B * N * 3 * H));
   TORCH_CHECK(D == 32 || D == 64);
   auto dqkv = torch::empty_like(qkv);
-  const int Npad = (N + 15) & ~15;
   const int nwaves = N > 96 ? 8 : 4;
   dim3 grid(B * H), block(nwaves * 64);
-  const int lds_kv = (2 * Npad * dla::KPAD + 2 * D * (Npad + 8) +
-                      nwaves * 2 * dla::PBUF) * 2;
-  const int lds_q = (2 * Npad * dla::KPAD + D * (Npad + 8) +
-                     nwaves * 2 * dla::PBUF) * 2;
+  const std::vector<int64_t> lds = attn_bwd_lds_bytes(N, D);
+  const int lds_kv = (int)lds[0];
+  const int lds_q = (int)lds[1];
+  TORCH_CHECK(lds_kv <= 163840 && lds_q <= 163840, "attn_bwd: N = ", N,
+              ", d = ", D, " needs ", lds_kv, " B of LDS (limit 163840); "
+              "use attn_bwd_stream");
   auto run = [&](auto dtag) {
     constexpr int DD = decltype(dtag)::value;
     hipLaunchKernelGGL((dla::attn_bwd_kv_kernel<DD>), grid, block, lds_kv,

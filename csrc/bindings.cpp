@@ -147,11 +147,21 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor qkv, int64_t num_heads,
 std::vector<torch::Tensor> attn_bwd(torch::Tensor qkv, torch::Tensor dout,
                                     torch::Tensor stats, torch::Tensor drow,
                                     int64_t num_heads, double scale);
+std::vector<int64_t> attn_bwd_lds_bytes(int64_t N, int64_t D);
 std::vector<torch::Tensor> attn_fwd_cosine(torch::Tensor qkv, int64_t num_heads,
                               torch::Tensor logit_scale,
                               c10::optional<torch::Tensor> bias,
                               c10::optional<torch::Tensor> mask, bool save_p);
 torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor B);
+// attention_stream.hip
+std::vector<torch::Tensor> attn_fwd_stream(torch::Tensor qkv,
+                                           int64_t num_heads, double scale,
+                                           bool save_stats);
+std::vector<torch::Tensor> attn_bwd_stream(torch::Tensor qkv,
+                                           torch::Tensor dout,
+                                           torch::Tensor stats,
+                                           torch::Tensor drow,
+                                           int64_t num_heads, double scale);
 // my_add.cpp (custom-op export tutorial)
 torch::Tensor my_add(torch::Tensor a, torch::Tensor b);
 // cocoeval.cpp (CPU)
@@ -228,10 +238,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("mask") = py::none(), py::arg("save_p") = false,
         py::arg("save_stats") = false);
   m.def("attn_bwd", &attn_bwd);
+  m.def("attn_bwd_lds_bytes", &attn_bwd_lds_bytes);
   m.def("attn_fwd_cosine", &attn_fwd_cosine, py::arg("qkv"),
         py::arg("num_heads"), py::arg("logit_scale"),
         py::arg("bias") = py::none(), py::arg("mask") = py::none(),
         py::arg("save_p") = false);
+  m.def("attn_fwd_stream", &attn_fwd_stream, py::arg("qkv"),
+        py::arg("num_heads"), py::arg("scale"), py::arg("save_stats") = false);
+  m.def("attn_bwd_stream", &attn_bwd_stream);
   m.def("mfma_probe", &mfma_probe);
   m.def("cocoeval_match_image", &cocoeval_match_image, py::arg("det_boxes"),
         py::arg("det_scores"), py::arg("gt_boxes"), py::arg("gt_crowd"),

@@ -35,17 +35,73 @@ def _eager_attention(qkv: torch.Tensor, num_heads: int, scale: float,
     return out
 
 
+_RESIDENT_MAX_N = 256    # resident kernels: whole score row in s_acc[16]
+_STREAM_MAX_N = 4096     # streaming kernels (csrc/attention_stream.hip)
+_LDS_LIMIT = 160 * 1024  # bytes of LDS per CU on gfx950
+
+
+def _resident_bwd_lds_bytes(N: int, d: int) -> tuple[int, int]:
+    """Dynamic LDS bytes (kv kernel, q kernel) of the resident backward:
+    the arithmetic of attn_bwd_lds_bytes in csrc/attention.hip."""
+    kpad, pbuf = 72, 16 * 72
+    npad = (N + 15) & ~15
+    nwaves = 8 if N > 96 else 4
+    lds_kv = (2 * npad * kpad + 2 * d * (npad + 8) + nwaves * 2 * pbuf) * 2
+    lds_q = (2 * npad * kpad + d * (npad + 8) + nwaves * 2 * pbuf) * 2
+    return lds_kv, lds_q
+
+
+def _force_stream() -> bool:
+    import os
+    return os.environ.get("DLA_ATTN_STREAM", "0") == "1"  # A/B testing only
+
+
+def _attn_route(N: int, d: int, dtype: torch.dtype, has_bias_or_mask: bool,
+                on_hip: bool) -> tuple[str, str]:
+    """(forward, backward) kernels for one attention call: each "resident"
+    (csrc/attention.hip), "stream" (csrc/attention_stream.hip) or "eager".
+
+    on_hip is use_hip(qkv): False on a CPU and under DLA_FORCE_EAGER=1. The
+    route is decided by arithmetic alone, never by trying a launch. The
+    bias/mask (and cosine) paths have resident kernels only; their backward
+    runs from the saved P and has no LDS limit of its own.
+    DLA_ATTN_STREAM=1 forces "stream" wherever it is legal (A/B only).
+    """
+    if (not on_hip or dtype != torch.bfloat16 or d not in (32, 64)
+            or N < 1 or N > _STREAM_MAX_N):
+        return "eager", "eager"
+    if has_bias_or_mask:
+        if N <= _RESIDENT_MAX_N:
+            return "resident", "resident"
+        return "eager", "eager"
+    if _force_stream():
+        return "stream", "stream"
+    fwd = "resident" if N <= _RESIDENT_MAX_N else "stream"
+    bwd = "stream"
+    if fwd == "resident" and \
+            max(_resident_bwd_lds_bytes(N, d)) <= _LDS_LIMIT:
+        bwd = "resident"
+    return fwd, bwd
+
+
 class _AttnFusedBwdFn(torch.autograd.Function):
     """No-bias/mask path: forward saves only per-row softmax stats; backward
-    recomputes P in-LDS (two HIP kernels, no [B,H,N,N] tensor ever hits HBM)."""
+    recomputes P in-LDS (two HIP kernels, no [B,H,N,N] tensor ever hits HBM).
+    route = (fwd, bwd) from _attn_route; the resident and streaming kernels
+    share the stats layout, so the two halves are routed independently."""
 
     @staticmethod
-    def forward(ctx, qkv, num_heads, scale):
+    def forward(ctx, qkv, num_heads, scale, route=("resident", "resident")):
         needs = qkv.requires_grad
-        res = ext().attn_fwd(qkv.contiguous(), num_heads, scale, None, None,
-                             False, needs)
+        if route[0] == "stream":
+            res = ext().attn_fwd_stream(qkv.contiguous(), num_heads, scale,
+                                        needs)
+        else:
+            res = ext().attn_fwd(qkv.contiguous(), num_heads, scale, None,
+                                 None, False, needs)
         ctx.num_heads = num_heads
         ctx.scale = scale
+        ctx.bwd_route = route[1]
         if needs:
             ctx.save_for_backward(qkv, res[0], res[1])
         return res[0]
@@ -59,9 +115,10 @@ class _AttnFusedBwdFn(torch.autograd.Function):
         # D_row[b,h,n] = sum_d dO * O  (one fused reduce)
         drow = (dout.float() * out.float()).view(B, N, H, -1).sum(-1) \
             .permute(0, 2, 1).contiguous()
-        (dqkv,) = ext().attn_bwd(qkv, dout.to(qkv.dtype), stats, drow, H,
-                                 ctx.scale)
-        return dqkv, None, None
+        bwd = ext().attn_bwd_stream if ctx.bwd_route == "stream" \
+            else ext().attn_bwd
+        (dqkv,) = bwd(qkv, dout.to(qkv.dtype), stats, drow, H, ctx.scale)
+        return dqkv, None, None, None
 
 
 class _AttnFn(torch.autograd.Function):
@@ -109,15 +166,17 @@ def fused_attention(qkv: torch.Tensor, num_heads: int, scale: float,
 
     bias: [H, N, N] additive (relative position bias); mask: [nW, N, N]
     additive window mask (Swin). Falls back to eager off-GPU or out of the
-    kernel's shape domain (d in {32,64}, N <= 256, bf16).
+    kernels' shape domain (bf16, d in {32,64}; N <= 4096 on the plain path,
+    N <= 256 with a bias or mask) — see _attn_route.
     """
     d = qkv.shape[2] // (3 * num_heads)
-    if (use_hip(qkv) and qkv.dtype == torch.bfloat16 and d in (32, 64)
-            and qkv.shape[1] <= 256):
-        if bias is None and mask is None:
-            return _AttnFusedBwdFn.apply(qkv, num_heads, scale)
-        return _AttnFn.apply(qkv, num_heads, scale, bias, mask)
-    return _eager_attention(qkv, num_heads, scale, bias, mask)
+    plain = bias is None and mask is None
+    route = _attn_route(qkv.shape[1], d, qkv.dtype, not plain, use_hip(qkv))
+    if route[0] == "eager":
+        return _eager_attention(qkv, num_heads, scale, bias, mask)
+    if plain:
+        return _AttnFusedBwdFn.apply(qkv, num_heads, scale, route)
+    return _AttnFn.apply(qkv, num_heads, scale, bias, mask)
 
 
 class _AttnCosineFn(torch.autograd.Function):
