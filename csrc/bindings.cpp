@@ -123,6 +123,18 @@ torch::Tensor softmax_ce_bwd(torch::Tensor logits,
                              torch::Tensor lse, double smoothing,
                              int64_t ignore_index, torch::Tensor grad_out,
                              torch::Tensor stats);
+// dense_ce.hip
+std::vector<torch::Tensor> dense_ce_fwd(torch::Tensor logits,
+                                        torch::Tensor target,
+                                        c10::optional<torch::Tensor> weight,
+                                        int64_t ignore_index, int64_t reduction,
+                                        bool channels_last);
+torch::Tensor dense_ce_bwd(torch::Tensor logits, torch::Tensor target,
+                           c10::optional<torch::Tensor> weight,
+                           torch::Tensor lse, int64_t ignore_index,
+                           int64_t reduction, bool channels_last,
+                           torch::Tensor grad_out,
+                           c10::optional<torch::Tensor> stats);
 // focal.hip
 torch::Tensor focal_loss_fwd(torch::Tensor logits, torch::Tensor targets,
                              double alpha, double gamma);
@@ -227,6 +239,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("stride2_scatter", &stride2_scatter);
   m.def("softmax_ce_fwd", &softmax_ce_fwd);
   m.def("softmax_ce_bwd", &softmax_ce_bwd);
+  m.def("dense_ce_fwd", &dense_ce_fwd);
+  m.def("dense_ce_bwd", &dense_ce_bwd);
   m.def("focal_loss_fwd", &focal_loss_fwd);
   m.def("focal_loss_bwd", &focal_loss_bwd);
   m.def("box_iou", &box_iou_gpu);

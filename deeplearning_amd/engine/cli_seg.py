@@ -23,6 +23,7 @@ from ..core.meters import AverageMeter
 from ..engine.metrics import ConfusionMatrix, dice_loss
 from ..engine.scheduler import WarmupScheduler
 from ..models import build_model
+from ..ops.losses import dense_cross_entropy
 
 
 class SyntheticSegmentation(Dataset):
@@ -81,15 +82,15 @@ def seg_criterion(outputs, target, aux_weight=0.5, use_dice=False,
     if ohem is not None:
         loss = ohem(out, target)
     else:
-        loss = F.cross_entropy(out, target, ignore_index=255)
+        loss = dense_cross_entropy(out, target, ignore_index=255)
     if use_dice:
         nc = out.shape[1]
         onehot = F.one_hot(target.clamp(0, nc - 1), nc)
         onehot = onehot.permute(0, 3, 1, 2).float()
         loss = loss + dice_loss(out, onehot)
     if isinstance(outputs, dict) and "aux" in outputs:
-        loss = loss + aux_weight * F.cross_entropy(outputs["aux"], target,
-                                                   ignore_index=255)
+        loss = loss + aux_weight * dense_cross_entropy(
+            outputs["aux"], target, ignore_index=255)
     return loss
 
 

@@ -13,6 +13,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ...ops import BatchNorm2d
+from ...ops.losses import dense_ce_fused, dense_cross_entropy
 from ..classification.resnet import BasicBlock, Bottleneck
 from ..registry import register_model
 
@@ -152,16 +153,25 @@ class OhemCrossEntropy(nn.Module):
         self.min_kept = max(1, min_kept)
 
     def forward(self, logits, target):
-        pred = F.softmax(logits, dim=1)
-        pixel_losses = F.cross_entropy(
-            logits, target, ignore_index=self.ignore_label,
-            reduction="none").contiguous().view(-1)
-        mask = target.contiguous().view(-1) != self.ignore_label
+        if dense_ce_fused(logits, target):
+            # one fused pass: the target-class probability softmax_t =
+            # exp(z_t - lse) is exp(-loss), so no softmax and no gather
+            pixel_losses = dense_cross_entropy(
+                logits, target, ignore_index=self.ignore_label,
+                reduction="none").view(-1)
+            mask = target.contiguous().view(-1) != self.ignore_label
+            pred, ind = torch.exp(-pixel_losses.detach())[mask].sort()
+        else:
+            pred = F.softmax(logits, dim=1)
+            pixel_losses = F.cross_entropy(
+                logits, target, ignore_index=self.ignore_label,
+                reduction="none").contiguous().view(-1)
+            mask = target.contiguous().view(-1) != self.ignore_label
 
-        tmp_target = target.clone()
-        tmp_target[tmp_target == self.ignore_label] = 0
-        pred = pred.gather(1, tmp_target.unsqueeze(1)).squeeze(1)
-        pred, ind = pred.contiguous().view(-1)[mask].contiguous().sort()
+            tmp_target = target.clone()
+            tmp_target[tmp_target == self.ignore_label] = 0
+            pred = pred.gather(1, tmp_target.unsqueeze(1)).squeeze(1)
+            pred, ind = pred.contiguous().view(-1)[mask].contiguous().sort()
         if pred.numel() == 0:
             return pixel_losses.sum() * 0
         min_value = pred[min(self.min_kept, pred.numel() - 1)]

@@ -9,8 +9,8 @@ from .drop import DropPath, drop_path
 from .dwconv import DepthwiseConv2d, can_use_dwconv, depthwise_conv2d
 from .ema import ModelEMA
 from .layernorm import LayerNorm, LayerNorm2d, layer_norm
-from .losses import (CrossEntropyLoss, cross_entropy, sigmoid_focal_loss,
-                     soft_target_cross_entropy)
+from .losses import (CrossEntropyLoss, cross_entropy, dense_cross_entropy,
+                     sigmoid_focal_loss, soft_target_cross_entropy)
 from .roi_align import MultiScaleRoIAlign, roi_align
 from .stem import bn_relu_maxpool, can_fuse_stem
 from .window import (roll_and_window_partition, window_merge_and_roll,
@@ -28,7 +28,7 @@ __all__ = [
     "DropPath", "drop_path", "ModelEMA",
     "LayerNorm", "LayerNorm2d", "layer_norm",
     "CrossEntropyLoss", "cross_entropy", "soft_target_cross_entropy",
-    "sigmoid_focal_loss",
+    "sigmoid_focal_loss", "dense_cross_entropy",
     "MultiScaleRoIAlign", "roi_align",
     "roll_and_window_partition", "window_merge_and_roll",
     "window_partition_eager", "window_reverse_eager",

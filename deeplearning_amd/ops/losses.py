@@ -1,5 +1,5 @@
 """Loss ops backed by HIP kernels: fused softmax-CE (label smoothing, soft
-targets) and sigmoid focal loss.
+targets), per-pixel CE for dense prediction, and sigmoid focal loss.
 
 Reference parity: nn.CrossEntropyLoss everywhere; timm
 LabelSmoothingCrossEntropy / SoftTargetCrossEntropy (swin main.py:111-117);
@@ -7,6 +7,8 @@ sigmoid_focal_loss (RetinaNet network_files/losses.py:5-50, FCOS
 models/loss.py:344-364).
 """
 from __future__ import annotations
+
+import os
 
 import torch
 import torch.nn as nn
@@ -50,11 +52,98 @@ class _SoftmaxCEFn(torch.autograd.Function):
         return dlogits, None, None, None, None
 
 
+_DENSE_CE_MAX_C_NHWC = 256  # the channels_last kernels' LDS tile limit
+_REDUCTIONS = {"none": 0, "sum": 1, "mean": 2}
+
+
+def _is_channels_last(t: torch.Tensor) -> bool:
+    return (t.dim() == 4 and not t.is_contiguous()
+            and t.is_contiguous(memory_format=torch.channels_last))
+
+
+class _DenseCEFn(torch.autograd.Function):
+    """Per-pixel CE on [B, C, *spatial] logits, one kernel pass forward and one
+    backward, in the logits' own dtype and layout (NCHW or channels_last).
+    The reduced loss and its denominator stay on the device (stats[2]), so
+    nothing syncs the host. custom_fwd/custom_bwd keep autocast from touching
+    the logits: they go to the kernel as they are."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda")
+    def forward(ctx, logits, target, weight, ignore_index, reduction):
+        cl = _is_channels_last(logits)
+        if not cl:
+            logits = logits.contiguous()
+        target = target.contiguous()
+        if weight is not None:
+            weight = weight.detach().float().contiguous()
+        red = _REDUCTIONS[reduction]
+        res, lse = ext().dense_ce_fwd(logits, target, weight, ignore_index,
+                                      red, cl)
+        ctx.save_for_backward(logits, target, lse, weight, res if red else None)
+        ctx.args = (ignore_index, red, cl)
+        return res[0] if red else res
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, dloss):
+        logits, target, lse, weight, stats = ctx.saved_tensors
+        ignore_index, red, cl = ctx.args
+        grad_out = dloss.detach().float()
+        if not grad_out.is_cuda:  # backward of a CPU-held scalar grad
+            grad_out = grad_out.to(logits.device)
+        grad_out = grad_out.reshape(1) if red else grad_out.contiguous()
+        dlogits = ext().dense_ce_bwd(logits, target, weight, lse, ignore_index,
+                                     red, cl, grad_out, stats)
+        return dlogits, None, None, None, None
+
+
+def dense_ce_fused(logits: torch.Tensor, target: torch.Tensor) -> bool:
+    """True iff dense_cross_entropy takes the HIP kernels for these inputs."""
+    if os.environ.get("DLA_DENSE_CE", "1") == "0":  # A/B testing only
+        return False
+    if logits.dim() < 3 or target.dtype != torch.long or logits.numel() == 0:
+        return False
+    if logits.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        return False
+    if _is_channels_last(logits) and logits.shape[1] > _DENSE_CE_MAX_C_NHWC:
+        return False
+    return use_hip(logits, target)
+
+
+def dense_cross_entropy(logits: torch.Tensor, target: torch.Tensor,
+                        weight: torch.Tensor | None = None,
+                        ignore_index: int = 255,
+                        reduction: str = "mean") -> torch.Tensor:
+    """Per-pixel CE for dense prediction. logits [B, C, *spatial] (fp32, bf16
+    or fp16; contiguous or channels_last, any other strides take one
+    .contiguous()), target int64 [B, *spatial], weight [C] or None.
+
+    On the GPU this is one fused HIP pass forward and one backward, with the
+    semantics of F.cross_entropy except:
+      - the result is always fp32 (what eager returns under autocast);
+      - a target outside [0, C) counts as ignored (eager device-asserts), so
+        no label check ever needs a host sync;
+      - reduction="mean" over no valid pixel (or zero summed weight) is 0 with
+        a zero gradient, not NaN: the 2-D op's convention.
+    channels_last logits with C > 256, probability targets, the CPU,
+    DLA_FORCE_EAGER=1 and DLA_DENSE_CE=0 take F.cross_entropy itself."""
+    if reduction not in _REDUCTIONS:
+        raise ValueError(f"reduction must be none, sum or mean: {reduction!r}")
+    if dense_ce_fused(logits, target):
+        return _DenseCEFn.apply(logits, target, weight, ignore_index, reduction)
+    return F.cross_entropy(logits, target, weight=weight,
+                           ignore_index=ignore_index, reduction=reduction)
+
+
 def cross_entropy(logits: torch.Tensor, target: torch.Tensor,
                   smoothing: float = 0.0, ignore_index: int = -100) -> torch.Tensor:
-    """Mean CE over valid rows. target: int64 class ids (B,)."""
+    """Mean CE over valid rows. target: int64 class ids (B,), or
+    (B, *spatial) for dense (B, C, *spatial) logits."""
     if use_hip(logits) and logits.dim() == 2:
         return _SoftmaxCEFn.apply(logits, target, None, smoothing, ignore_index)
+    if logits.dim() >= 3 and smoothing == 0:
+        return dense_cross_entropy(logits, target, ignore_index=ignore_index)
     return F.cross_entropy(logits, target, label_smoothing=smoothing,
                            ignore_index=ignore_index)
 
