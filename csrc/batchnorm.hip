@@ -204,16 +204,9 @@ __global__ void bn_bwd_dx_kernel(const dev_t* __restrict__ dy,
 // lanes_per_row)*V, row = t / lanes_per_row), rows strided by
 // used_threads/lanes_per_row. Adjacent lanes read adjacent 16B channel chunks
 // (fully coalesced); per-channel parameters load ONCE per thread (c0 is
-// loop-invariant). That is the mapping of the apply and dx kernels; the
-// per-channel reduction kernels have their own, below.
-
-inline int64_t nhwc_used_threads(int lanes_per_row, int64_t rows,
-                                 int64_t target_lanes) {
-  int64_t k = target_lanes / lanes_per_row;
-  if (k > rows) k = rows;
-  if (k < 1) k = 1;
-  return (int64_t)lanes_per_row * k;
-}
+// loop-invariant). That is the mapping of the apply and dx kernels
+// (used_threads is nhwc_used_threads of common.h); the per-channel reduction
+// kernels have their own, below.
 
 // ---- NHWC per-channel reductions: no atomics, one slab row per block -------
 // The reduction kernels (stats, backward stats, join backward stats, stem
@@ -685,9 +678,145 @@ __global__ void bn_join_bwd_dx_dual_nhwc_kernel(
   }
 }
 
-inline bool is_nhwc(const torch::Tensor& t) {
-  return t.dim() == 4 && t.is_contiguous(at::MemoryFormat::ChannelsLast) &&
-         !t.is_contiguous();
+// ============================== host layer ===================================
+// Every kernel is launched from ONE host function: a bn_*_launch below, or for
+// the stem kernels their one entry point. A launcher owns its kernel's grid
+// rule, its choice of vector width and the tensors the kernel produces. The
+// bound entry points are compositions: bn_geom and the other checks, the
+// parameter conversions, launchers, the packaging of the result.
+
+// Two layout predicates; both meanings are in use.
+// Any channels-last-contiguous 4-D tensor, [N, C, 1, 1] and [N, 1, H, W]
+// (NCHW-contiguous as well) included: the joins, the dx-only entries and the
+// stem, whose kernels see a [rows, C] matrix and nothing else.
+inline bool is_nhwc_rows(const torch::Tensor& t) {
+  return t.dim() == 4 && t.is_contiguous(at::MemoryFormat::ChannelsLast);
+}
+
+// Channels-last and NOT NCHW-contiguous: batchnorm_fwd,
+// batchnorm_fwd_from_sums, bn_apply and batchnorm_bwd_ex route on this one, so
+// a tensor that is both takes their NCHW kernels.
+inline bool is_nhwc_not_nchw(const torch::Tensor& t) {
+  return is_nhwc_rows(t) && !t.is_contiguous();
+}
+
+template <typename dev_t>
+constexpr int kVecMax = 16 / (int)sizeof(dev_t);  // 16-byte vectors
+
+struct BnGeom {
+  bool nhwc;  // x takes the NHWC kernels
+  int N, C, H, W;
+  int64_t HW, rows;  // rows = N * H * W
+};
+
+enum class BnLayout {
+  kNchwOrNhwc,  // NHWC kernels iff is_nhwc_not_nchw, else NCHW-contiguous
+  kNhwcRows,    // is_nhwc_rows, full-width vectors only
+};
+
+// The checks every entry makes on x (device, dtype, 4-D, layout) and x's
+// geometry. The joins, the dx-only entries and the stem (kNhwcRows) have
+// kernels for V = VMAX alone, so they require C % VMAX == 0.
+inline BnGeom bn_geom(const torch::Tensor& x, const char* fn, BnLayout layout) {
+  TORCH_CHECK(x.is_cuda(), fn, ": x must be a GPU tensor");
+  TORCH_CHECK(x.dim() == 4, fn, " expects a 4D tensor");
+  const auto st = x.scalar_type();
+  TORCH_CHECK(st == torch::kFloat || st == torch::kBFloat16 ||
+                  st == torch::kHalf, fn, ": unsupported dtype ", st);
+  BnGeom geo;
+  if (layout == BnLayout::kNhwcRows) {
+    const int vmax = 16 / (int)x.element_size();
+    TORCH_CHECK(is_nhwc_rows(x), fn, ": x must be channels_last");
+    TORCH_CHECK(x.size(1) % vmax == 0, fn, ": C must be a multiple of ", vmax);
+    geo.nhwc = true;
+  } else {
+    geo.nhwc = is_nhwc_not_nchw(x);
+    TORCH_CHECK(geo.nhwc || x.is_contiguous(), fn,
+                ": x must be contiguous (NCHW or channels_last)");
+  }
+  geo.N = (int)x.size(0), geo.C = (int)x.size(1);
+  geo.H = (int)x.size(2), geo.W = (int)x.size(3);
+  geo.HW = x.size(2) * x.size(3);
+  geo.rows = (int64_t)geo.N * geo.HW;
+  return geo;
+}
+
+// Per-channel tensors have C elements; where the entry hands their pointers
+// to a kernel unconverted (fp32_contig) they are contiguous fp32 GPU tensors.
+inline void bn_check_channels(std::initializer_list<const torch::Tensor*> ts,
+                              int C, const char* fn, bool fp32_contig = false) {
+  for (const auto* t : ts) {
+    TORCH_CHECK(t->numel() == C, fn,
+                ": per-channel tensors must have C elements");
+    TORCH_CHECK(!fp32_contig ||
+                    (t->is_cuda() && t->scalar_type() == torch::kFloat &&
+                     t->is_contiguous()),
+                fn, ": per-channel tensors must be contiguous fp32 [C]");
+  }
+}
+
+// Grid of the NHWC elementwise kernels (apply, dx, join, stem dx): `used`
+// threads in whole rows of C / V lanes, in blocks of 256.
+constexpr int64_t kNhwcLaneTarget = 524288;
+
+struct NhwcGrid {
+  int64_t used;
+  int blocks;
+};
+
+inline NhwcGrid nhwc_grid(int lanes_per_row, int64_t rows) {
+  const int64_t used = nhwc_used_threads(lanes_per_row, rows, kNhwcLaneTarget);
+  return {used, (int)((used + 255) / 256)};
+}
+
+// gridDim.y of the NCHW reduction kernels (gridDim.x = C).
+inline int nchw_ysplit(const BnGeom& geo) {
+  return (int)std::min<int64_t>((geo.rows + 65535) / 65536 + 1,
+                                std::max(1, 2048 / geo.C));
+}
+
+// f(integral_constant V). The NHWC reduction kernels (forward and backward
+// statistics) take V = VMAX, 2 or 1, whichever divides C.
+template <typename dev_t, typename F>
+inline void bn_red_vec(int C, F&& f) {
+  if (C % kVecMax<dev_t> == 0) f(std::integral_constant<int, kVecMax<dev_t>>{});
+  else if (C % 2 == 0) f(std::integral_constant<int, 2>{});
+  else f(std::integral_constant<int, 1>{});
+}
+
+// The elementwise kernels (apply, dx) take V = VMAX or 1, never 2.
+template <typename dev_t, typename F>
+inline void bn_elt_vec(bool vec_ok, F&& f) {
+  if (vec_ok) f(std::integral_constant<int, kVecMax<dev_t>>{});
+  else f(std::integral_constant<int, 1>{});
+}
+
+// Forward pass 1. NCHW: the [2C] {sum, sumsq} vector, zeroed because
+// bn_stats_kernel adds into it. NHWC: the kernel's [n_parts, 2C] slab, which
+// the finalize kernel sums.
+inline torch::Tensor bn_stats_launch(const torch::Tensor& x, const BnGeom& geo) {
+  const auto opts_f = x.options().dtype(torch::kFloat);
+  const int C = geo.C;
+  torch::Tensor sums;
+  DLA_DISPATCH_FLOAT_TYPES(x.scalar_type(), "bn_stats", [&] {
+    if (!geo.nhwc) {
+      sums = torch::zeros({2 * C}, opts_f);
+      hipLaunchKernelGGL((bn_stats_kernel<dev_t>), dim3(C, nchw_ysplit(geo)),
+                         dim3(256), 0, stream(), (const dev_t*)x.data_ptr(),
+                         sums.data_ptr<float>(), geo.N, C, geo.HW);
+      return;
+    }
+    bn_red_vec<dev_t>(C, [&](auto vtag) {
+      constexpr int V = decltype(vtag)::value;
+      const auto t = nhwc_red_tile(C / V, geo.rows);
+      sums = torch::empty({t.parts, 2 * C}, opts_f);
+      hipLaunchKernelGGL((bn_stats_nhwc_kernel<dev_t, V>),
+                         dim3(t.chunks, t.parts), dim3(kRedThreads), 0,
+                         stream(), (const dev_t*)x.data_ptr(),
+                         sums.data_ptr<float>(), C, geo.rows, t.bl, t.rb);
+    });
+  });
+  return sums;
 }
 
 struct BnFinalized {
@@ -737,6 +866,42 @@ inline BnFinalized bn_finalize_launch(
   return f;
 }
 
+// y = x * scale[c] + shift[c] (+ReLU); scale and shift contiguous fp32 [C].
+// NHWC vectorises along C. NCHW vectorises along HW (HW % VMAX, not C), where
+// a vector stays inside one channel.
+inline torch::Tensor bn_apply_launch(const torch::Tensor& x, const BnGeom& geo,
+                                     const torch::Tensor& scale,
+                                     const torch::Tensor& shift, bool relu) {
+  auto y = torch::empty_like(x);
+  DLA_DISPATCH_FLOAT_TYPES(x.scalar_type(), "bn_apply", [&] {
+    const bool vec_ok = (geo.nhwc ? geo.C : geo.HW) % kVecMax<dev_t> == 0;
+    bn_elt_vec<dev_t>(vec_ok, [&](auto vtag) {
+      constexpr int V = decltype(vtag)::value;
+      auto launch = [&](auto rtag) {
+        constexpr bool R = decltype(rtag)::value;
+        if (geo.nhwc) {
+          const auto grid = nhwc_grid(geo.C / V, geo.rows);
+          hipLaunchKernelGGL((bn_apply_nhwc_kernel<dev_t, V, R>),
+                             dim3(grid.blocks), dim3(256), 0, stream(),
+                             (const dev_t*)x.data_ptr(), scale.data_ptr<float>(),
+                             shift.data_ptr<float>(), (dev_t*)y.data_ptr(),
+                             geo.C, geo.rows, grid.used);
+        } else {
+          const int64_t n_total = x.numel();
+          hipLaunchKernelGGL((bn_apply_kernel<dev_t, V, R>),
+                             dim3(grid_1d((n_total + V - 1) / V, 256)),
+                             dim3(256), 0, stream(), (const dev_t*)x.data_ptr(),
+                             scale.data_ptr<float>(), shift.data_ptr<float>(),
+                             (dev_t*)y.data_ptr(), geo.C, geo.HW, n_total);
+        }
+      };
+      if (relu) launch(std::true_type{});
+      else launch(std::false_type{});
+    });
+  });
+  return y;
+}
+
 // dweight / dbias as views of the backward sums buffer: no device copy when
 // the parameter is fp32, one conversion otherwise.
 inline torch::Tensor bn_param_grad(const torch::Tensor& sums, int64_t offset,
@@ -767,8 +932,100 @@ inline torch::Tensor bn_slab_reduce_launch(const torch::Tensor& slab) {
   return sums;
 }
 
-inline bool is_nhwc_rows(const torch::Tensor& t) {
-  return t.dim() == 4 && t.is_contiguous(at::MemoryFormat::ChannelsLast);
+// What a backward reads of one BN: its input, the saved statistics and the
+// weight in fp32.
+struct BnSaved {
+  torch::Tensor x, mean, rstd, w32;
+};
+
+// Where the ReLU mask of a BN(+ReLU) backward comes from: the stored y
+// (MASK_Y), or x through the forward's scale and shift. All null without ReLU.
+struct BnMask {
+  const void* y = nullptr;
+  const float* scale = nullptr;
+  const float* shift = nullptr;
+};
+
+// Backward pass 1: the [2C] {sum g, sum g*xhat}. NCHW adds into a zeroed
+// vector and has no mask-from-x variant; NHWC sums its slab in a fixed order.
+template <bool R, bool MY>
+inline torch::Tensor bn_bwd_stats_launch(const torch::Tensor& dy, const BnSaved& bn,
+                                         const BnMask& mask, const BnGeom& geo) {
+  const auto opts_f = bn.x.options().dtype(torch::kFloat);
+  const int C = geo.C;
+  torch::Tensor sums;
+  DLA_DISPATCH_FLOAT_TYPES(bn.x.scalar_type(), "bn_bwd_stats", [&] {
+    if (geo.nhwc) {
+      bn_red_vec<dev_t>(C, [&](auto vtag) {
+        constexpr int V = decltype(vtag)::value;
+        const auto t = nhwc_red_tile(C / V, geo.rows);
+        auto slab = torch::empty({t.parts, 2 * C}, opts_f);
+        hipLaunchKernelGGL((bn_bwd_stats_nhwc_kernel<dev_t, V, R, MY>),
+                           dim3(t.chunks, t.parts), dim3(kRedThreads), 0,
+                           stream(), (const dev_t*)dy.data_ptr(),
+                           (const dev_t*)bn.x.data_ptr(), (const dev_t*)mask.y,
+                           mask.scale, mask.shift, bn.mean.data_ptr<float>(),
+                           bn.rstd.data_ptr<float>(), slab.data_ptr<float>(), C,
+                           geo.rows, t.bl, t.rb);
+        sums = bn_slab_reduce_launch(slab);
+      });
+    } else if constexpr (!R || MY) {
+      sums = torch::zeros({2 * C}, opts_f);
+      hipLaunchKernelGGL((bn_bwd_stats_kernel<dev_t, R>),
+                         dim3(C, nchw_ysplit(geo)), dim3(256), 0, stream(),
+                         (const dev_t*)dy.data_ptr(),
+                         (const dev_t*)bn.x.data_ptr(), (const dev_t*)mask.y,
+                         bn.mean.data_ptr<float>(), bn.rstd.data_ptr<float>(),
+                         sums.data_ptr<float>(), geo.N, C, geo.HW);
+    }
+  });
+  return sums;
+}
+
+// Backward pass 2: dx from dy (or from the masked g, with R = false) and the
+// [2C] sums.
+template <bool R, bool MY>
+inline torch::Tensor bn_bwd_dx_launch(const torch::Tensor& dy, const BnSaved& bn,
+                                      const BnMask& mask,
+                                      const torch::Tensor& sums,
+                                      const BnGeom& geo) {
+  auto dx = torch::empty_like(bn.x);
+  const float inv_count = 1.f / (float)geo.rows;
+  DLA_DISPATCH_FLOAT_TYPES(bn.x.scalar_type(), "bn_bwd_dx", [&] {
+    if (geo.nhwc) {
+      bn_elt_vec<dev_t>(geo.C % kVecMax<dev_t> == 0, [&](auto vtag) {
+        constexpr int V = decltype(vtag)::value;
+        const auto grid = nhwc_grid(geo.C / V, geo.rows);
+        hipLaunchKernelGGL((bn_bwd_dx_nhwc_kernel<dev_t, V, R, MY>),
+                           dim3(grid.blocks), dim3(256), 0, stream(),
+                           (const dev_t*)dy.data_ptr(),
+                           (const dev_t*)bn.x.data_ptr(), (const dev_t*)mask.y,
+                           mask.scale, mask.shift, bn.mean.data_ptr<float>(),
+                           bn.rstd.data_ptr<float>(), bn.w32.data_ptr<float>(),
+                           sums.data_ptr<float>(), (dev_t*)dx.data_ptr(),
+                           geo.C, geo.rows, grid.used, inv_count);
+      });
+    } else if constexpr (!R || MY) {
+      const int64_t n_total = bn.x.numel();
+      hipLaunchKernelGGL((bn_bwd_dx_kernel<dev_t, R>),
+                         dim3(grid_1d(n_total, 256)), dim3(256), 0, stream(),
+                         (const dev_t*)dy.data_ptr(),
+                         (const dev_t*)bn.x.data_ptr(), (const dev_t*)mask.y,
+                         bn.mean.data_ptr<float>(), bn.rstd.data_ptr<float>(),
+                         bn.w32.data_ptr<float>(), sums.data_ptr<float>(),
+                         (dev_t*)dx.data_ptr(), geo.C, geo.HW, n_total,
+                         inv_count);
+    }
+  });
+  return dx;
+}
+
+// {dx, dweight, dbias} of one BN from its dx and [2C] sums.
+inline std::vector<torch::Tensor> bn_grads(const torch::Tensor& dx,
+                                           const torch::Tensor& sums, int C,
+                                           const torch::Tensor& weight) {
+  return {dx, bn_param_grad(sums, C, C, weight),
+          bn_param_grad(sums, 0, C, weight)};
 }
 
 }  // namespace dla
@@ -781,101 +1038,17 @@ std::vector<torch::Tensor> batchnorm_fwd(torch::Tensor x, torch::Tensor weight,
                                          c10::optional<torch::Tensor> running_mean,
                                          c10::optional<torch::Tensor> running_var,
                                          double momentum, double eps, bool relu) {
-  DLA_CHECK_CUDA(x);
-  TORCH_CHECK(x.dim() == 4, "batchnorm_fwd expects a 4D tensor");
-  const bool nhwc = dla::is_nhwc(x);
-  TORCH_CHECK(nhwc || x.is_contiguous(), "batchnorm_fwd: x must be contiguous "
-              "(NCHW or channels_last)");
-  const int N = (int)x.size(0), C = (int)x.size(1);
-  const int64_t HW = x.size(2) * x.size(3);
-  auto opts_f = x.options().dtype(torch::kFloat);
-  // NCHW: the zeroed [2C] vector that bn_stats_kernel adds into. NHWC: the
-  // stats kernel's [n_parts, 2C] slab, summed by the finalize kernel.
-  auto sums = nhwc ? torch::Tensor() : torch::zeros({2 * C}, opts_f);
-  auto mean = torch::empty({C}, opts_f);
-  auto rstd = torch::empty({C}, opts_f);
-  auto scale = torch::empty({C}, opts_f);
-  auto shift = torch::empty({C}, opts_f);
-  auto y = torch::empty_like(x);
+  const auto geo = dla::bn_geom(x, "batchnorm_fwd", dla::BnLayout::kNchwOrNhwc);
+  // converted here, ahead of the statistics kernel as before; the finalize
+  // launcher's own conversion is then a no-op
   auto w32 = weight.to(torch::kFloat);
   auto b32 = bias.to(torch::kFloat);
-
-  const int64_t rows = (int64_t)N * HW;
-  const int ysplit = (int)std::min<int64_t>((rows + 65535) / 65536 + 1,
-                                            std::max(1, 2048 / C));
-  DLA_DISPATCH_FLOAT_TYPES(x.scalar_type(), "batchnorm_fwd", [&] {
-    if (nhwc) {
-      constexpr int VM = 16 / (int)sizeof(dev_t);
-      auto stats = [&](auto vtag) {
-        constexpr int V = decltype(vtag)::value;
-        const auto t = dla::nhwc_red_tile(C / V, rows);
-        sums = torch::empty({t.parts, 2 * C}, opts_f);
-        hipLaunchKernelGGL((dla::bn_stats_nhwc_kernel<dev_t, V>),
-                           dim3(t.chunks, t.parts), dim3(dla::kRedThreads), 0,
-                           dla::stream(), (const dev_t*)x.data_ptr(),
-                           sums.data_ptr<float>(), C, rows, t.bl, t.rb);
-      };
-      if (C % VM == 0) stats(std::integral_constant<int, VM>{});
-      else if (C % 2 == 0) stats(std::integral_constant<int, 2>{});
-      else stats(std::integral_constant<int, 1>{});
-    } else {
-      hipLaunchKernelGGL((dla::bn_stats_kernel<dev_t>), dim3(C, ysplit), dim3(256), 0,
-                         dla::stream(), (const dev_t*)x.data_ptr(),
-                         sums.data_ptr<float>(), N, C, HW);
-    }
-    float* rm = running_mean.has_value() ? running_mean->data_ptr<float>() : nullptr;
-    float* rv = running_var.has_value() ? running_var->data_ptr<float>() : nullptr;
-    if (sums.dim() == 2 && sums.size(0) > 1) {
-      hipLaunchKernelGGL(dla::bn_finalize_parts_kernel,
-                         dim3((C + dla::kFinCh - 1) / dla::kFinCh),
-                         dim3(dla::kFinCh * dla::kFinRows), 0, dla::stream(),
-                         sums.data_ptr<float>(), (int)sums.size(0),
-                         w32.data_ptr<float>(), b32.data_ptr<float>(),
-                         mean.data_ptr<float>(), rstd.data_ptr<float>(), rm, rv,
-                         scale.data_ptr<float>(), shift.data_ptr<float>(), C,
-                         (float)rows, (float)eps, (float)momentum);
-    } else {
-      hipLaunchKernelGGL(dla::bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0,
-                         dla::stream(), sums.data_ptr<float>(), w32.data_ptr<float>(),
-                         b32.data_ptr<float>(), mean.data_ptr<float>(),
-                         rstd.data_ptr<float>(), rm, rv,
-                         scale.data_ptr<float>(), shift.data_ptr<float>(), C,
-                         (float)rows, (float)eps, (float)momentum);
-    }
-    const int64_t n_total = x.numel();
-    constexpr int VMAX = 16 / (int)sizeof(dev_t);
-    auto launch = [&](auto vtag, auto rtag) {
-      constexpr int V = decltype(vtag)::value;
-      constexpr bool R = decltype(rtag)::value;
-      if (nhwc) {
-        const int lanes = C / V;
-        const int64_t used = dla::nhwc_used_threads(lanes, rows, 524288);
-        hipLaunchKernelGGL((dla::bn_apply_nhwc_kernel<dev_t, V, R>),
-                           dim3((int)((used + 255) / 256)), dim3(256), 0,
-                           dla::stream(), (const dev_t*)x.data_ptr(),
-                           scale.data_ptr<float>(), shift.data_ptr<float>(),
-                           (dev_t*)y.data_ptr(), C, rows, used);
-        return;
-      }
-      const int grid = dla::grid_1d((n_total + V - 1) / V, 256);
-      if (false) ;
-      else
-        hipLaunchKernelGGL((dla::bn_apply_kernel<dev_t, V, R>), dim3(grid), dim3(256),
-                           0, dla::stream(), (const dev_t*)x.data_ptr(),
-                           scale.data_ptr<float>(), shift.data_ptr<float>(),
-                           (dev_t*)y.data_ptr(), C, HW, n_total);
-    };
-    const bool vec_ok = nhwc ? (C % VMAX == 0) : (HW % VMAX == 0);
-    if (vec_ok) {
-      if (relu) launch(std::integral_constant<int, VMAX>{}, std::true_type{});
-      else launch(std::integral_constant<int, VMAX>{}, std::false_type{});
-    } else {
-      if (relu) launch(std::integral_constant<int, 1>{}, std::true_type{});
-      else launch(std::integral_constant<int, 1>{}, std::false_type{});
-    }
-  });
+  auto sums = dla::bn_stats_launch(x, geo);
+  auto fin = dla::bn_finalize_launch(sums, w32, b32, running_mean, running_var,
+                                     geo.C, geo.rows, momentum, eps);
+  auto y = dla::bn_apply_launch(x, geo, fin.scale, fin.shift, relu);
   HIP_CHECK_ERR();
-  return {y, mean, rstd, scale, shift};
+  return {y, fin.mean, fin.rstd, fin.scale, fin.shift};
 }
 
 // Train-mode BN forward with the stats pass ALREADY DONE by the producing
@@ -888,103 +1061,21 @@ std::vector<torch::Tensor> batchnorm_fwd_from_sums(
     torch::Tensor sums, c10::optional<torch::Tensor> running_mean,
     c10::optional<torch::Tensor> running_var, double momentum, double eps,
     bool relu) {
-  DLA_CHECK_CUDA(x);
-  TORCH_CHECK(x.dim() == 4, "batchnorm_fwd_from_sums expects a 4D tensor");
-  const bool nhwc = dla::is_nhwc(x);
-  TORCH_CHECK(nhwc || x.is_contiguous(),
-              "batchnorm_fwd_from_sums: x must be contiguous");
-  const int N = (int)x.size(0), C = (int)x.size(1);
-  const int64_t HW = x.size(2) * x.size(3);
-  auto y = torch::empty_like(x);
-  const int64_t rows = (int64_t)N * HW;
+  const auto geo = dla::bn_geom(x, "batchnorm_fwd_from_sums",
+                                dla::BnLayout::kNchwOrNhwc);
   auto fin = dla::bn_finalize_launch(sums, weight, bias, running_mean,
-                                     running_var, C, rows, momentum, eps);
-  auto& mean = fin.mean;
-  auto& rstd = fin.rstd;
-  auto& scale = fin.scale;
-  auto& shift = fin.shift;
-  DLA_DISPATCH_FLOAT_TYPES(x.scalar_type(), "batchnorm_fwd_from_sums", [&] {
-    const int64_t n_total = x.numel();
-    constexpr int VMAX = 16 / (int)sizeof(dev_t);
-    auto launch = [&](auto vtag, auto rtag) {
-      constexpr int V = decltype(vtag)::value;
-      constexpr bool R = decltype(rtag)::value;
-      if (nhwc) {
-        const int lanes = C / V;
-        const int64_t used = dla::nhwc_used_threads(lanes, rows, 524288);
-        hipLaunchKernelGGL((dla::bn_apply_nhwc_kernel<dev_t, V, R>),
-                           dim3((int)((used + 255) / 256)), dim3(256), 0,
-                           dla::stream(), (const dev_t*)x.data_ptr(),
-                           scale.data_ptr<float>(), shift.data_ptr<float>(),
-                           (dev_t*)y.data_ptr(), C, rows, used);
-        return;
-      }
-      const int grid = dla::grid_1d((n_total + V - 1) / V, 256);
-      hipLaunchKernelGGL((dla::bn_apply_kernel<dev_t, V, R>), dim3(grid),
-                         dim3(256), 0, dla::stream(),
-                         (const dev_t*)x.data_ptr(), scale.data_ptr<float>(),
-                         shift.data_ptr<float>(), (dev_t*)y.data_ptr(), C, HW,
-                         n_total);
-    };
-    const bool vec_ok = nhwc ? (C % VMAX == 0) : (HW % VMAX == 0);
-    if (vec_ok) {
-      if (relu) launch(std::integral_constant<int, VMAX>{}, std::true_type{});
-      else launch(std::integral_constant<int, VMAX>{}, std::false_type{});
-    } else {
-      if (relu) launch(std::integral_constant<int, 1>{}, std::true_type{});
-      else launch(std::integral_constant<int, 1>{}, std::false_type{});
-    }
-  });
+                                     running_var, geo.C, geo.rows, momentum, eps);
+  auto y = dla::bn_apply_launch(x, geo, fin.scale, fin.shift, relu);
   HIP_CHECK_ERR();
-  return {y, mean, rstd, scale, shift};
+  return {y, fin.mean, fin.rstd, fin.scale, fin.shift};
 }
 
 // Frozen/eval BN apply (+optional ReLU): per-channel scale/shift precomputed host-side.
 torch::Tensor bn_apply(torch::Tensor x, torch::Tensor scale, torch::Tensor shift,
                        bool relu) {
-  DLA_CHECK_CUDA(x);
-  TORCH_CHECK(x.dim() == 4, "bn_apply expects a 4D tensor");
-  const bool nhwc = dla::is_nhwc(x);
-  TORCH_CHECK(nhwc || x.is_contiguous(), "bn_apply: x must be contiguous");
-  const int C = (int)x.size(1);
-  const int64_t HW = x.size(2) * x.size(3);
-  auto y = torch::empty_like(x);
-  auto sc = scale.to(torch::kFloat).contiguous();
-  auto sh = shift.to(torch::kFloat).contiguous();
-  const int64_t n_total = x.numel();
-  DLA_DISPATCH_FLOAT_TYPES(x.scalar_type(), "bn_apply", [&] {
-    constexpr int VMAX = 16 / (int)sizeof(dev_t);
-    auto launch = [&](auto vtag, auto rtag) {
-      constexpr int V = decltype(vtag)::value;
-      constexpr bool R = decltype(rtag)::value;
-      if (nhwc) {
-        const int64_t rows = n_total / C;
-        const int lanes = C / V;
-        const int64_t used = dla::nhwc_used_threads(lanes, rows, 524288);
-        hipLaunchKernelGGL((dla::bn_apply_nhwc_kernel<dev_t, V, R>),
-                           dim3((int)((used + 255) / 256)), dim3(256), 0,
-                           dla::stream(), (const dev_t*)x.data_ptr(),
-                           sc.data_ptr<float>(), sh.data_ptr<float>(),
-                           (dev_t*)y.data_ptr(), C, rows, used);
-        return;
-      }
-      const int grid = dla::grid_1d((n_total + V - 1) / V, 256);
-      if (false) ;
-      else
-        hipLaunchKernelGGL((dla::bn_apply_kernel<dev_t, V, R>), dim3(grid), dim3(256),
-                           0, dla::stream(), (const dev_t*)x.data_ptr(),
-                           sc.data_ptr<float>(), sh.data_ptr<float>(),
-                           (dev_t*)y.data_ptr(), C, HW, n_total);
-    };
-    const bool vec_ok = nhwc ? (C % VMAX == 0) : (HW % VMAX == 0);
-    if (vec_ok) {
-      if (relu) launch(std::integral_constant<int, VMAX>{}, std::true_type{});
-      else launch(std::integral_constant<int, VMAX>{}, std::false_type{});
-    } else {
-      if (relu) launch(std::integral_constant<int, 1>{}, std::true_type{});
-      else launch(std::integral_constant<int, 1>{}, std::false_type{});
-    }
-  });
+  const auto geo = dla::bn_geom(x, "bn_apply", dla::BnLayout::kNchwOrNhwc);
+  auto y = dla::bn_apply_launch(x, geo, scale.to(torch::kFloat).contiguous(),
+                                shift.to(torch::kFloat).contiguous(), relu);
   HIP_CHECK_ERR();
   return y;
 }
@@ -993,7 +1084,7 @@ torch::Tensor bn_apply(torch::Tensor x, torch::Tensor scale, torch::Tensor shift
 // channels-last x takes it from x (bn_pre(x, scale, shift) > 0, no y read);
 // NCHW x keeps reading the stored y. The Python autograd functions ask this
 // same function in forward to decide whether y has to be saved.
-bool bn_relu_mask_from_x(torch::Tensor x) { return dla::is_nhwc(x); }
+bool bn_relu_mask_from_x(torch::Tensor x) { return dla::is_nhwc_not_nchw(x); }
 
 // Returns {dx, dweight, dbias}. relu=true needs a mask source: the forward's
 // scale and shift (channels-last only, see bn_relu_mask_from_x), or else y.
@@ -1003,107 +1094,42 @@ std::vector<torch::Tensor> batchnorm_bwd_ex(
     torch::Tensor weight, torch::Tensor mean, torch::Tensor rstd,
     c10::optional<torch::Tensor> scale, c10::optional<torch::Tensor> shift,
     bool relu) {
-  DLA_CHECK_CUDA(dy); DLA_CHECK_CUDA(x);
-  const bool nhwc = dla::is_nhwc(x);
-  TORCH_CHECK(nhwc || x.is_contiguous(), "batchnorm_bwd: x must be contiguous");
-  if (nhwc && !dla::is_nhwc(dy)) dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
-  if (!nhwc) dy = dy.contiguous();
-  const int N = (int)x.size(0), C = (int)x.size(1);
-  const int64_t HW = x.size(2) * x.size(3);
-  const int64_t rows = (int64_t)N * HW;
-  auto opts_f = x.options().dtype(torch::kFloat);
-  // NCHW: zeroed, bn_bwd_stats_kernel adds. NHWC: the slab's fixed-order sum.
-  auto sums = nhwc ? torch::Tensor() : torch::zeros({2 * C}, opts_f);
-  auto dx = torch::empty_like(x);
+  DLA_CHECK_CUDA(dy);
+  const auto geo = dla::bn_geom(x, "batchnorm_bwd", dla::BnLayout::kNchwOrNhwc);
+  if (geo.nhwc && !dla::is_nhwc_not_nchw(dy))
+    dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
+  if (!geo.nhwc) dy = dy.contiguous();
   auto w32 = weight.to(torch::kFloat);
-  const int ysplit = (int)std::min<int64_t>((rows + 65535) / 65536 + 1,
-                                            std::max(1, 2048 / C));
+  const dla::BnSaved bn{x, mean, rstd, w32};
   const bool mask_y = relu && y.has_value();
+  dla::BnMask mask;
   if (relu && !mask_y) {
     TORCH_CHECK(bn_relu_mask_from_x(x) && scale.has_value() && shift.has_value(),
                 "batchnorm_bwd: the relu mask needs y, or channels_last x "
                 "with the forward's scale and shift");
-    for (const auto* t : {&*scale, &*shift})
-      TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kFloat &&
-                      t->is_contiguous() && t->numel() == C,
-                  "batchnorm_bwd: scale/shift must be contiguous fp32 [C]");
+    dla::bn_check_channels({&*scale, &*shift}, geo.C, "batchnorm_bwd", true);
+    mask.scale = scale->data_ptr<float>();
+    mask.shift = shift->data_ptr<float>();
   }
-  if (mask_y)
+  if (mask_y) {
     TORCH_CHECK(y->scalar_type() == x.scalar_type() && y->sizes() == x.sizes() &&
-                    (nhwc ? dla::is_nhwc(*y) : y->is_contiguous()),
+                    (geo.nhwc ? dla::is_nhwc_not_nchw(*y) : y->is_contiguous()),
                 "batchnorm_bwd: y must match x (shape, dtype, layout)");
-  const float* scp = (relu && !mask_y) ? scale->data_ptr<float>() : nullptr;
-  const float* shp = (relu && !mask_y) ? shift->data_ptr<float>() : nullptr;
-  DLA_DISPATCH_FLOAT_TYPES(x.scalar_type(), "batchnorm_bwd", [&] {
-    const dev_t* yp = mask_y ? (const dev_t*)y->data_ptr() : nullptr;
-    // (RELU, MASK_Y) as compile-time tags: (false,false), (true,false), (true,true)
-    auto with_mode = [&](auto f) {
-      if (!relu) f(std::false_type{}, std::false_type{});
-      else if (mask_y) f(std::true_type{}, std::true_type{});
-      else f(std::true_type{}, std::false_type{});
-    };
-    with_mode([&](auto rtag, auto mtag) {
-      constexpr bool R = decltype(rtag)::value;
-      constexpr bool MY = decltype(mtag)::value;
-      if (nhwc) {
-        constexpr int VM = 16 / (int)sizeof(dev_t);
-        auto stats = [&](auto vtag) {
-          constexpr int V = decltype(vtag)::value;
-          const auto t = dla::nhwc_red_tile(C / V, rows);
-          auto slab = torch::empty({t.parts, 2 * C}, opts_f);
-          hipLaunchKernelGGL((dla::bn_bwd_stats_nhwc_kernel<dev_t, V, R, MY>),
-                             dim3(t.chunks, t.parts), dim3(dla::kRedThreads),
-                             0, dla::stream(), (const dev_t*)dy.data_ptr(),
-                             (const dev_t*)x.data_ptr(), yp, scp, shp,
-                             mean.data_ptr<float>(), rstd.data_ptr<float>(),
-                             slab.data_ptr<float>(), C, rows, t.bl, t.rb);
-          sums = dla::bn_slab_reduce_launch(slab);
-        };
-        if (C % VM == 0) stats(std::integral_constant<int, VM>{});
-        else if (C % 2 == 0) stats(std::integral_constant<int, 2>{});
-        else stats(std::integral_constant<int, 1>{});
-      } else if constexpr (!R || MY) {
-        hipLaunchKernelGGL((dla::bn_bwd_stats_kernel<dev_t, R>), dim3(C, ysplit),
-                           dim3(256), 0, dla::stream(), (const dev_t*)dy.data_ptr(),
-                           (const dev_t*)x.data_ptr(), yp, mean.data_ptr<float>(),
-                           rstd.data_ptr<float>(), sums.data_ptr<float>(), N, C, HW);
-      }
-    });
-
-    const int64_t n_total = x.numel();
-    const float inv_count = 1.f / (float)rows;
-    constexpr int VMAX = 16 / (int)sizeof(dev_t);
-    with_mode([&](auto rtag, auto mtag) {
-      constexpr bool R = decltype(rtag)::value;
-      constexpr bool MY = decltype(mtag)::value;
-      if (nhwc) {
-        auto dxk = [&](auto vtag) {
-          constexpr int V = decltype(vtag)::value;
-          const int lanes = C / V;
-          const int64_t used = dla::nhwc_used_threads(lanes, rows, 524288);
-          hipLaunchKernelGGL((dla::bn_bwd_dx_nhwc_kernel<dev_t, V, R, MY>),
-                             dim3((int)((used + 255) / 256)), dim3(256), 0,
-                             dla::stream(), (const dev_t*)dy.data_ptr(),
-                             (const dev_t*)x.data_ptr(), yp, scp, shp,
-                             mean.data_ptr<float>(), rstd.data_ptr<float>(),
-                             w32.data_ptr<float>(), sums.data_ptr<float>(),
-                             (dev_t*)dx.data_ptr(), C, rows, used, inv_count);
-        };
-        if (C % VMAX == 0) dxk(std::integral_constant<int, VMAX>{});
-        else dxk(std::integral_constant<int, 1>{});
-      } else if constexpr (!R || MY) {
-        hipLaunchKernelGGL((dla::bn_bwd_dx_kernel<dev_t, R>), dim3(dla::grid_1d(n_total, 256)),
-                           dim3(256), 0, dla::stream(), (const dev_t*)dy.data_ptr(),
-                           (const dev_t*)x.data_ptr(), yp, mean.data_ptr<float>(),
-                           rstd.data_ptr<float>(), w32.data_ptr<float>(),
-                           sums.data_ptr<float>(), (dev_t*)dx.data_ptr(), C, HW,
-                           n_total, inv_count);
-      }
-    });
-  });
+    mask.y = y->data_ptr();
+  }
+  torch::Tensor sums, dx;
+  // (RELU, MASK_Y) as compile-time tags: (false,false), (true,false), (true,true)
+  auto run = [&](auto rtag, auto mtag) {
+    constexpr bool R = decltype(rtag)::value;
+    constexpr bool MY = decltype(mtag)::value;
+    sums = dla::bn_bwd_stats_launch<R, MY>(dy, bn, mask, geo);
+    dx = dla::bn_bwd_dx_launch<R, MY>(dy, bn, mask, sums, geo);
+  };
+  if (!relu) run(std::false_type{}, std::false_type{});
+  else if (mask_y) run(std::true_type{}, std::true_type{});
+  else run(std::true_type{}, std::false_type{});
   HIP_CHECK_ERR();
-  return {dx, dla::bn_param_grad(sums, C, C, weight),
-          dla::bn_param_grad(sums, 0, C, weight)};
+  return dla::bn_grads(dx, sums, geo.C, weight);
 }
 
 // Today's signature: the mask comes from y.
@@ -1126,11 +1152,101 @@ inline void join_check(const torch::Tensor& x, const torch::Tensor& other,
               "bn join: ", what, " must match x (shape, dtype, channels_last)");
 }
 
-inline int join_vec(const torch::Tensor& x) {
-  const int vmax = 16 / (int)x.element_size();
-  TORCH_CHECK(x.size(1) % vmax == 0,
-              "bn join: C must be a multiple of ", vmax);
-  return vmax;
+// out = relu(bn(x) + other). fd null: other is the identity as it is; else
+// other is a raw conv output and fd its finalized BN (the dual join).
+inline torch::Tensor bn_add_relu_launch(const torch::Tensor& x,
+                                        const BnFinalized& fin,
+                                        const torch::Tensor& other,
+                                        const BnFinalized* fd,
+                                        const BnGeom& geo) {
+  auto out = torch::empty_like(x);
+  const float* scd = fd ? fd->scale.data_ptr<float>() : nullptr;
+  const float* shd = fd ? fd->shift.data_ptr<float>() : nullptr;
+  DLA_DISPATCH_FLOAT_TYPES(x.scalar_type(), "bn_add_relu", [&] {
+    constexpr int V = kVecMax<dev_t>;
+    const auto grid = nhwc_grid(geo.C / V, geo.rows);
+    auto launch = [&](auto dtag) {
+      hipLaunchKernelGGL(
+          (bn_add_relu_nhwc_kernel<dev_t, V, decltype(dtag)::value>),
+          dim3(grid.blocks), dim3(256), 0, stream(), (const dev_t*)x.data_ptr(),
+          fin.scale.data_ptr<float>(), fin.shift.data_ptr<float>(),
+          (const dev_t*)other.data_ptr(), scd, shd, (dev_t*)out.data_ptr(),
+          geo.C, geo.rows, grid.used);
+    };
+    if (fd) launch(std::true_type{});
+    else launch(std::false_type{});
+  });
+  return out;
+}
+
+// Join backward pass 1: writes g = dy * [out > 0] and returns the [NS*C] sums
+// {sum g, sum g*xhat, (dual) sum g*xhat_d}. bnd is the second BN of a dual
+// join, null for the single join.
+inline torch::Tensor bn_join_bwd_stats_launch(const torch::Tensor& dy,
+                                              const torch::Tensor& out,
+                                              const BnSaved& bn,
+                                              const BnSaved* bnd,
+                                              torch::Tensor& g,
+                                              const BnGeom& geo) {
+  const int C = geo.C;
+  torch::Tensor sums;
+  DLA_DISPATCH_FLOAT_TYPES(bn.x.scalar_type(), "bn_join_bwd_stats", [&] {
+    constexpr int V = kVecMax<dev_t>;
+    const dev_t* xd = bnd ? (const dev_t*)bnd->x.data_ptr() : nullptr;
+    const float* mean_d = bnd ? bnd->mean.data_ptr<float>() : nullptr;
+    const float* rstd_d = bnd ? bnd->rstd.data_ptr<float>() : nullptr;
+    const auto t = nhwc_red_tile(C / V, geo.rows);
+    auto slab = torch::empty({t.parts, (bnd ? 3 : 2) * C},
+                             bn.x.options().dtype(torch::kFloat));
+    auto launch = [&](auto dtag) {
+      hipLaunchKernelGGL(
+          (bn_join_bwd_stats_nhwc_kernel<dev_t, V, decltype(dtag)::value>),
+          dim3(t.chunks, t.parts), dim3(kRedThreads), 0, stream(),
+          (const dev_t*)dy.data_ptr(), (const dev_t*)out.data_ptr(),
+          (const dev_t*)bn.x.data_ptr(), bn.mean.data_ptr<float>(),
+          bn.rstd.data_ptr<float>(), xd, mean_d, rstd_d, (dev_t*)g.data_ptr(),
+          slab.data_ptr<float>(), C, geo.rows, t.bl, t.rb);
+    };
+    if (bnd) launch(std::true_type{});
+    else launch(std::false_type{});
+    sums = bn_slab_reduce_launch(slab);
+  });
+  return sums;
+}
+
+// Dual join backward pass 2: {dx, dxd} from one read of g and the [3C] sums.
+inline std::pair<torch::Tensor, torch::Tensor> bn_join_dual_dx_launch(
+    const torch::Tensor& g, const BnSaved& bn, const BnSaved& bnd,
+    const torch::Tensor& sums, const BnGeom& geo) {
+  auto dx = torch::empty_like(bn.x);
+  auto dxd = torch::empty_like(bn.x);
+  DLA_DISPATCH_FLOAT_TYPES(bn.x.scalar_type(), "bn_join_dual_dx", [&] {
+    constexpr int V = kVecMax<dev_t>;
+    const auto grid = nhwc_grid(geo.C / V, geo.rows);
+    hipLaunchKernelGGL((bn_join_bwd_dx_dual_nhwc_kernel<dev_t, V>),
+                       dim3(grid.blocks), dim3(256), 0, stream(),
+                       (const dev_t*)g.data_ptr(), (const dev_t*)bn.x.data_ptr(),
+                       (const dev_t*)bnd.x.data_ptr(), bn.mean.data_ptr<float>(),
+                       bn.rstd.data_ptr<float>(), bn.w32.data_ptr<float>(),
+                       bnd.mean.data_ptr<float>(), bnd.rstd.data_ptr<float>(),
+                       bnd.w32.data_ptr<float>(), sums.data_ptr<float>(),
+                       (dev_t*)dx.data_ptr(), (dev_t*)dxd.data_ptr(), geo.C,
+                       geo.rows, grid.used, 1.f / (float)geo.rows);
+  });
+  return {dx, dxd};
+}
+
+// {dx, dxd, dweight, dbias, dweight_d, dbias_d} of a dual join from its [3C]
+// sums. sum g serves both biases, but two parameters must not share gradient
+// storage (optimizers update .grad in place): the second gets a copy.
+inline std::vector<torch::Tensor> dual_grads(
+    const std::pair<torch::Tensor, torch::Tensor>& dxs,
+    const torch::Tensor& sums, int C, const torch::Tensor& weight,
+    const torch::Tensor& weight_d) {
+  auto dbias = bn_param_grad(sums, 0, C, weight);
+  return {dxs.first, dxs.second, bn_param_grad(sums, C, C, weight), dbias,
+          bn_param_grad(sums, 2 * C, C, weight_d),
+          dbias.to(weight_d.scalar_type()).clone()};
 }
 
 }  // namespace dla
@@ -1142,25 +1258,11 @@ std::vector<torch::Tensor> bn_add_relu_fwd_from_sums(
     torch::Tensor sums, c10::optional<torch::Tensor> running_mean,
     c10::optional<torch::Tensor> running_var, double momentum, double eps,
     torch::Tensor identity) {
-  DLA_CHECK_CUDA(x);
-  TORCH_CHECK(dla::is_nhwc_rows(x), "bn_add_relu: x must be channels_last");
+  const auto geo = dla::bn_geom(x, "bn_add_relu", dla::BnLayout::kNhwcRows);
   dla::join_check(x, identity, "identity");
-  dla::join_vec(x);
-  const int C = (int)x.size(1);
-  const int64_t rows = x.numel() / C;
   auto fin = dla::bn_finalize_launch(sums, weight, bias, running_mean,
-                                     running_var, C, rows, momentum, eps);
-  auto out = torch::empty_like(x);
-  DLA_DISPATCH_FLOAT_TYPES(x.scalar_type(), "bn_add_relu_fwd_from_sums", [&] {
-    constexpr int V = 16 / (int)sizeof(dev_t);
-    const int64_t used = dla::nhwc_used_threads(C / V, rows, 524288);
-    hipLaunchKernelGGL((dla::bn_add_relu_nhwc_kernel<dev_t, V, false>),
-                       dim3((int)((used + 255) / 256)), dim3(256), 0,
-                       dla::stream(), (const dev_t*)x.data_ptr(),
-                       fin.scale.data_ptr<float>(), fin.shift.data_ptr<float>(),
-                       (const dev_t*)identity.data_ptr(), nullptr, nullptr,
-                       (dev_t*)out.data_ptr(), C, rows, used);
-  });
+                                     running_var, geo.C, geo.rows, momentum, eps);
+  auto out = dla::bn_add_relu_launch(x, fin, identity, nullptr, geo);
   HIP_CHECK_ERR();
   return {out, fin.mean, fin.rstd};
 }
@@ -1175,28 +1277,14 @@ std::vector<torch::Tensor> bn_add_relu_dual_fwd_from_sums(
     torch::Tensor sums_d, c10::optional<torch::Tensor> running_mean_d,
     c10::optional<torch::Tensor> running_var_d, double momentum_d,
     double eps_d) {
-  DLA_CHECK_CUDA(x);
-  TORCH_CHECK(dla::is_nhwc_rows(x), "bn_add_relu_dual: x must be channels_last");
+  const auto geo = dla::bn_geom(x, "bn_add_relu_dual", dla::BnLayout::kNhwcRows);
   dla::join_check(x, xd, "xd");
-  dla::join_vec(x);
-  const int C = (int)x.size(1);
-  const int64_t rows = x.numel() / C;
   auto fin = dla::bn_finalize_launch(sums, weight, bias, running_mean,
-                                     running_var, C, rows, momentum, eps);
+                                     running_var, geo.C, geo.rows, momentum, eps);
   auto fd = dla::bn_finalize_launch(sums_d, weight_d, bias_d, running_mean_d,
-                                    running_var_d, C, rows, momentum_d, eps_d);
-  auto out = torch::empty_like(x);
-  DLA_DISPATCH_FLOAT_TYPES(x.scalar_type(), "bn_add_relu_dual_fwd_from_sums", [&] {
-    constexpr int V = 16 / (int)sizeof(dev_t);
-    const int64_t used = dla::nhwc_used_threads(C / V, rows, 524288);
-    hipLaunchKernelGGL((dla::bn_add_relu_nhwc_kernel<dev_t, V, true>),
-                       dim3((int)((used + 255) / 256)), dim3(256), 0,
-                       dla::stream(), (const dev_t*)x.data_ptr(),
-                       fin.scale.data_ptr<float>(), fin.shift.data_ptr<float>(),
-                       (const dev_t*)xd.data_ptr(), fd.scale.data_ptr<float>(),
-                       fd.shift.data_ptr<float>(), (dev_t*)out.data_ptr(), C,
-                       rows, used);
-  });
+                                    running_var_d, geo.C, geo.rows, momentum_d,
+                                    eps_d);
+  auto out = dla::bn_add_relu_launch(x, fin, xd, &fd, geo);
   HIP_CHECK_ERR();
   return {out, fin.mean, fin.rstd, fd.mean, fd.rstd};
 }
@@ -1207,48 +1295,20 @@ std::vector<torch::Tensor> bn_add_relu_bwd(torch::Tensor dy, torch::Tensor out,
                                            torch::Tensor x, torch::Tensor weight,
                                            torch::Tensor mean,
                                            torch::Tensor rstd) {
-  DLA_CHECK_CUDA(x);
-  TORCH_CHECK(dla::is_nhwc_rows(x), "bn_add_relu_bwd: x must be channels_last");
+  const auto geo = dla::bn_geom(x, "bn_add_relu_bwd", dla::BnLayout::kNhwcRows);
   dla::join_check(x, out, "out");
   if (!dla::is_nhwc_rows(dy)) dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
   dla::join_check(x, dy, "dy");
-  dla::join_vec(x);
-  const int C = (int)x.size(1);
-  const int64_t rows = x.numel() / C;
-  TORCH_CHECK(mean.numel() == C && rstd.numel() == C && weight.numel() == C,
-              "bn_add_relu_bwd: per-channel tensors must have C elements");
-  torch::Tensor sums;
+  dla::bn_check_channels({&mean, &rstd, &weight}, geo.C, "bn_add_relu_bwd");
   auto g = torch::empty_like(x);
-  auto dx = torch::empty_like(x);
   auto w32 = weight.to(torch::kFloat).contiguous();
-  DLA_DISPATCH_FLOAT_TYPES(x.scalar_type(), "bn_add_relu_bwd", [&] {
-    constexpr int V = 16 / (int)sizeof(dev_t);
-    const int lanes = C / V;
-    const auto t = dla::nhwc_red_tile(lanes, rows);
-    auto slab = torch::empty({t.parts, 2 * C},
-                             x.options().dtype(torch::kFloat));
-    hipLaunchKernelGGL((dla::bn_join_bwd_stats_nhwc_kernel<dev_t, V, false>),
-                       dim3(t.chunks, t.parts), dim3(dla::kRedThreads), 0,
-                       dla::stream(),
-                       (const dev_t*)dy.data_ptr(), (const dev_t*)out.data_ptr(),
-                       (const dev_t*)x.data_ptr(), mean.data_ptr<float>(),
-                       rstd.data_ptr<float>(), nullptr, nullptr, nullptr,
-                       (dev_t*)g.data_ptr(), slab.data_ptr<float>(), C, rows,
-                       t.bl, t.rb);
-    sums = dla::bn_slab_reduce_launch(slab);
-    const int64_t used = dla::nhwc_used_threads(lanes, rows, 524288);
-    hipLaunchKernelGGL((dla::bn_bwd_dx_nhwc_kernel<dev_t, V, false>),
-                       dim3((int)((used + 255) / 256)), dim3(256), 0,
-                       dla::stream(), (const dev_t*)g.data_ptr(),
-                       (const dev_t*)x.data_ptr(), nullptr, nullptr, nullptr,
-                       mean.data_ptr<float>(), rstd.data_ptr<float>(),
-                       w32.data_ptr<float>(), sums.data_ptr<float>(),
-                       (dev_t*)dx.data_ptr(), C, rows, used,
-                       1.f / (float)rows);
-  });
+  const dla::BnSaved bn{x, mean, rstd, w32};
+  auto sums = dla::bn_join_bwd_stats_launch(dy, out, bn, nullptr, g, geo);
+  // the mask is in g already: the plain dx pass without ReLU
+  auto dx = dla::bn_bwd_dx_launch<false, false>(g, bn, {}, sums, geo);
   HIP_CHECK_ERR();
-  return {g, dx, dla::bn_param_grad(sums, C, C, weight),
-          dla::bn_param_grad(sums, 0, C, weight)};
+  return {g, dx, dla::bn_param_grad(sums, geo.C, geo.C, weight),
+          dla::bn_param_grad(sums, 0, geo.C, weight)};
 }
 
 // Backward of the dual join. Returns {dx, dxd, dweight, dbias, dweight_d,
@@ -1257,72 +1317,34 @@ std::vector<torch::Tensor> bn_add_relu_dual_bwd(
     torch::Tensor dy, torch::Tensor out, torch::Tensor x, torch::Tensor weight,
     torch::Tensor mean, torch::Tensor rstd, torch::Tensor xd,
     torch::Tensor weight_d, torch::Tensor mean_d, torch::Tensor rstd_d) {
-  DLA_CHECK_CUDA(x);
-  TORCH_CHECK(dla::is_nhwc_rows(x), "bn_add_relu_dual_bwd: x must be channels_last");
+  const auto geo = dla::bn_geom(x, "bn_add_relu_dual_bwd",
+                                dla::BnLayout::kNhwcRows);
   dla::join_check(x, out, "out");
   dla::join_check(x, xd, "xd");
   if (!dla::is_nhwc_rows(dy)) dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
   dla::join_check(x, dy, "dy");
-  dla::join_vec(x);
-  const int C = (int)x.size(1);
-  const int64_t rows = x.numel() / C;
-  TORCH_CHECK(mean.numel() == C && rstd.numel() == C && weight.numel() == C &&
-                  mean_d.numel() == C && rstd_d.numel() == C &&
-                  weight_d.numel() == C,
-              "bn_add_relu_dual_bwd: per-channel tensors must have C elements");
-  torch::Tensor sums;
+  dla::bn_check_channels({&mean, &rstd, &weight, &mean_d, &rstd_d, &weight_d},
+                         geo.C, "bn_add_relu_dual_bwd");
   auto g = torch::empty_like(x);
-  auto dx = torch::empty_like(x);
-  auto dxd = torch::empty_like(x);
   auto w32 = weight.to(torch::kFloat).contiguous();
   auto wd32 = weight_d.to(torch::kFloat).contiguous();
-  DLA_DISPATCH_FLOAT_TYPES(x.scalar_type(), "bn_add_relu_dual_bwd", [&] {
-    constexpr int V = 16 / (int)sizeof(dev_t);
-    const int lanes = C / V;
-    const auto t = dla::nhwc_red_tile(lanes, rows);
-    auto slab = torch::empty({t.parts, 3 * C},
-                             x.options().dtype(torch::kFloat));
-    hipLaunchKernelGGL((dla::bn_join_bwd_stats_nhwc_kernel<dev_t, V, true>),
-                       dim3(t.chunks, t.parts), dim3(dla::kRedThreads), 0,
-                       dla::stream(),
-                       (const dev_t*)dy.data_ptr(), (const dev_t*)out.data_ptr(),
-                       (const dev_t*)x.data_ptr(), mean.data_ptr<float>(),
-                       rstd.data_ptr<float>(), (const dev_t*)xd.data_ptr(),
-                       mean_d.data_ptr<float>(), rstd_d.data_ptr<float>(),
-                       (dev_t*)g.data_ptr(), slab.data_ptr<float>(), C, rows,
-                       t.bl, t.rb);
-    sums = dla::bn_slab_reduce_launch(slab);
-    const int64_t used = dla::nhwc_used_threads(lanes, rows, 524288);
-    hipLaunchKernelGGL((dla::bn_join_bwd_dx_dual_nhwc_kernel<dev_t, V>),
-                       dim3((int)((used + 255) / 256)), dim3(256), 0,
-                       dla::stream(), (const dev_t*)g.data_ptr(),
-                       (const dev_t*)x.data_ptr(), (const dev_t*)xd.data_ptr(),
-                       mean.data_ptr<float>(), rstd.data_ptr<float>(),
-                       w32.data_ptr<float>(), mean_d.data_ptr<float>(),
-                       rstd_d.data_ptr<float>(), wd32.data_ptr<float>(),
-                       sums.data_ptr<float>(), (dev_t*)dx.data_ptr(),
-                       (dev_t*)dxd.data_ptr(), C, rows, used,
-                       1.f / (float)rows);
-  });
+  const dla::BnSaved bn{x, mean, rstd, w32}, bnd{xd, mean_d, rstd_d, wd32};
+  auto sums = dla::bn_join_bwd_stats_launch(dy, out, bn, &bnd, g, geo);
+  auto dxs = dla::bn_join_dual_dx_launch(g, bn, bnd, sums, geo);
   HIP_CHECK_ERR();
-  // sum g serves both biases, but two parameters must not share gradient
-  // storage (optimizers update .grad in place): the second gets a copy
-  auto dbias = dla::bn_param_grad(sums, 0, C, weight);
-  return {dx, dxd, dla::bn_param_grad(sums, C, C, weight), dbias,
-          dla::bn_param_grad(sums, 2 * C, C, weight_d),
-          dbias.to(weight_d.scalar_type()).clone()};
+  return dla::dual_grads(dxs, sums, geo.C, weight, weight_d);
 }
 
 // ---- dx-only backward: pass 1 ran in the conv1x1 dgrad epilogue -------------
 // g is the masked gradient that epilogue stored and slab its [n_parts, NS*C]
 // partial sums (conv1x1_dgrad_bwdstats), so what is left is the slab reduce
 // and the dx pass. Serves BatchNorm(+ReLU) and the single join alike: with the
-// mask already in g both are bn_bwd_dx_nhwc_kernel<.., false>.
+// mask already in g both are bn_bwd_dx_nhwc_kernel<.., false>. The epilogue
+// is bf16, so these entries are bf16 with V = 8.
 namespace dla {
 
 inline void dx_only_check(const torch::Tensor& x, const torch::Tensor& g,
                           const torch::Tensor& slab, int ns) {
-  TORCH_CHECK(is_nhwc_rows(x), "bn dx-only: x must be channels_last");
   join_check(x, g, "g");
   TORCH_CHECK(x.scalar_type() == torch::kBFloat16, "bn dx-only: bf16 only");
   TORCH_CHECK(slab.is_cuda() && slab.scalar_type() == torch::kFloat &&
@@ -1352,28 +1374,16 @@ std::vector<torch::Tensor> bn_bwd_dx_from_slab(torch::Tensor g,
                                                torch::Tensor weight,
                                                torch::Tensor mean,
                                                torch::Tensor rstd) {
-  DLA_CHECK_CUDA(x);
+  const auto geo = dla::bn_geom(x, "bn_bwd_dx_from_slab",
+                                dla::BnLayout::kNhwcRows);
   dla::dx_only_check(x, g, slab, 2);
-  const int V = dla::join_vec(x);
-  const int C = (int)x.size(1);
-  const int64_t rows = x.numel() / C;
-  TORCH_CHECK(mean.numel() == C && rstd.numel() == C && weight.numel() == C,
-              "bn_bwd_dx_from_slab: per-channel tensors must have C elements");
-  auto dx = torch::empty_like(x);
+  dla::bn_check_channels({&mean, &rstd, &weight}, geo.C, "bn_bwd_dx_from_slab");
   auto w32 = weight.to(torch::kFloat).contiguous();
   auto sums = dla::bn_slab_reduce_launch(slab);
-  using dev_t = __hip_bfloat16;
-  const int64_t used = dla::nhwc_used_threads(C / V, rows, 524288);
-  hipLaunchKernelGGL((dla::bn_bwd_dx_nhwc_kernel<dev_t, 8, false>),
-                     dim3((int)((used + 255) / 256)), dim3(256), 0,
-                     dla::stream(), (const dev_t*)g.data_ptr(),
-                     (const dev_t*)x.data_ptr(), nullptr, nullptr, nullptr,
-                     mean.data_ptr<float>(), rstd.data_ptr<float>(),
-                     w32.data_ptr<float>(), sums.data_ptr<float>(),
-                     (dev_t*)dx.data_ptr(), C, rows, used, 1.f / (float)rows);
+  auto dx = dla::bn_bwd_dx_launch<false, false>(g, {x, mean, rstd, w32}, {},
+                                                sums, geo);
   HIP_CHECK_ERR();
-  return {dx, dla::bn_param_grad(sums, C, C, weight),
-          dla::bn_param_grad(sums, 0, C, weight)};
+  return dla::bn_grads(dx, sums, geo.C, weight);
 }
 
 // Dual join. Returns {dx, dxd, dweight, dbias, dweight_d, dbias_d}.
@@ -1381,39 +1391,19 @@ std::vector<torch::Tensor> bn_join_dual_bwd_dx_from_slab(
     torch::Tensor g, torch::Tensor slab, torch::Tensor x, torch::Tensor weight,
     torch::Tensor mean, torch::Tensor rstd, torch::Tensor xd,
     torch::Tensor weight_d, torch::Tensor mean_d, torch::Tensor rstd_d) {
-  DLA_CHECK_CUDA(x);
+  const auto geo = dla::bn_geom(x, "bn_join_dual_bwd_dx_from_slab",
+                                dla::BnLayout::kNhwcRows);
   dla::dx_only_check(x, g, slab, 3);
   dla::join_check(x, xd, "xd");
-  const int V = dla::join_vec(x);
-  const int C = (int)x.size(1);
-  const int64_t rows = x.numel() / C;
-  TORCH_CHECK(mean.numel() == C && rstd.numel() == C && weight.numel() == C &&
-                  mean_d.numel() == C && rstd_d.numel() == C &&
-                  weight_d.numel() == C,
-              "bn_join_dual_bwd_dx_from_slab: per-channel tensors must have C "
-              "elements");
-  auto dx = torch::empty_like(x);
-  auto dxd = torch::empty_like(x);
+  dla::bn_check_channels({&mean, &rstd, &weight, &mean_d, &rstd_d, &weight_d},
+                         geo.C, "bn_join_dual_bwd_dx_from_slab");
   auto w32 = weight.to(torch::kFloat).contiguous();
   auto wd32 = weight_d.to(torch::kFloat).contiguous();
   auto sums = dla::bn_slab_reduce_launch(slab);
-  using dev_t = __hip_bfloat16;
-  const int64_t used = dla::nhwc_used_threads(C / V, rows, 524288);
-  hipLaunchKernelGGL((dla::bn_join_bwd_dx_dual_nhwc_kernel<dev_t, 8>),
-                     dim3((int)((used + 255) / 256)), dim3(256), 0,
-                     dla::stream(), (const dev_t*)g.data_ptr(),
-                     (const dev_t*)x.data_ptr(), (const dev_t*)xd.data_ptr(),
-                     mean.data_ptr<float>(), rstd.data_ptr<float>(),
-                     w32.data_ptr<float>(), mean_d.data_ptr<float>(),
-                     rstd_d.data_ptr<float>(), wd32.data_ptr<float>(),
-                     sums.data_ptr<float>(), (dev_t*)dx.data_ptr(),
-                     (dev_t*)dxd.data_ptr(), C, rows, used,
-                     1.f / (float)rows);
+  auto dxs = dla::bn_join_dual_dx_launch(g, {x, mean, rstd, w32},
+                                         {xd, mean_d, rstd_d, wd32}, sums, geo);
   HIP_CHECK_ERR();
-  auto dbias = dla::bn_param_grad(sums, 0, C, weight);
-  return {dx, dxd, dla::bn_param_grad(sums, C, C, weight), dbias,
-          dla::bn_param_grad(sums, 2 * C, C, weight_d),
-          dbias.to(weight_d.scalar_type()).clone()};
+  return dla::dual_grads(dxs, sums, geo.C, weight, weight_d);
 }
 
 // ---- fused stem: BN apply + ReLU + 3x3 / stride 2 / pad 1 max-pool ----------
@@ -1618,13 +1608,12 @@ __global__ void bn_relu_maxpool_bwd_dx_nhwc_kernel(
   }
 }
 
-inline void stem_check(const torch::Tensor& x, const char* fn) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 4 && is_nhwc_rows(x), fn,
-              ": x must be a channels_last 4D GPU tensor");
-  const int vmax = 16 / (int)x.element_size();
-  TORCH_CHECK(x.size(1) % vmax == 0, fn, ": C must be a multiple of ", vmax);
-  TORCH_CHECK(x.numel() > 0 && x.numel() / x.size(1) < (int64_t(1) << 31),
-              fn, ": N*H*W must be in [1, 2^31)");
+// x of a stem entry (the stem kernels index rows with 32 bits).
+inline BnGeom stem_geom(const torch::Tensor& x, const char* fn) {
+  const auto geo = bn_geom(x, fn, BnLayout::kNhwcRows);
+  TORCH_CHECK(x.numel() > 0 && geo.rows < (int64_t(1) << 31), fn,
+              ": N*H*W must be in [1, 2^31)");
+  return geo;
 }
 
 }  // namespace dla
@@ -1635,29 +1624,20 @@ std::vector<torch::Tensor> bn_relu_maxpool_fwd(
     torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
     c10::optional<torch::Tensor> running_mean,
     c10::optional<torch::Tensor> running_var, double momentum, double eps) {
-  dla::stem_check(x, "bn_relu_maxpool_fwd");
-  const int N = (int)x.size(0), C = (int)x.size(1);
-  const int H = (int)x.size(2), W = (int)x.size(3);
+  const auto geo = dla::stem_geom(x, "bn_relu_maxpool_fwd");
+  const int N = geo.N, C = geo.C, H = geo.H, W = geo.W;
   const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
-  const int64_t rows = (int64_t)N * H * W;
   auto out_opts = x.options().memory_format(at::MemoryFormat::ChannelsLast);
   auto pooled = torch::empty({N, C, OH, OW}, out_opts);
   auto slots = torch::empty({N, C, OH, OW}, out_opts.dtype(torch::kByte));
   const int runs = (OH + dla::kPoolRun - 1) / dla::kPoolRun;
   TORCH_CHECK((int64_t)N * runs < (int64_t(1) << 31),
               "bn_relu_maxpool_fwd: too many blocks");
-  dla::BnFinalized fin;
+  auto sums = dla::bn_stats_launch(x, geo);
+  auto fin = dla::bn_finalize_launch(sums, weight, bias, running_mean,
+                                     running_var, C, geo.rows, momentum, eps);
   DLA_DISPATCH_FLOAT_TYPES(x.scalar_type(), "bn_relu_maxpool_fwd", [&] {
-    constexpr int V = 16 / (int)sizeof(dev_t);
-    const auto t = dla::nhwc_red_tile(C / V, rows);
-    auto sums = torch::empty({t.parts, 2 * C},
-                             x.options().dtype(torch::kFloat));
-    hipLaunchKernelGGL((dla::bn_stats_nhwc_kernel<dev_t, V>),
-                       dim3(t.chunks, t.parts), dim3(dla::kRedThreads), 0,
-                       dla::stream(), (const dev_t*)x.data_ptr(),
-                       sums.data_ptr<float>(), C, rows, t.bl, t.rb);
-    fin = dla::bn_finalize_launch(sums, weight, bias, running_mean,
-                                  running_var, C, rows, momentum, eps);
+    constexpr int V = dla::kVecMax<dev_t>;
     hipLaunchKernelGGL((dla::bn_relu_maxpool_fwd_nhwc_kernel<dev_t, V>),
                        dim3(N * runs), dim3(256), 0, dla::stream(),
                        (const dev_t*)x.data_ptr(), fin.scale.data_ptr<float>(),
@@ -1673,36 +1653,30 @@ std::vector<torch::Tensor> bn_relu_maxpool_bwd(
     torch::Tensor dpool, torch::Tensor x, torch::Tensor slots,
     torch::Tensor weight, torch::Tensor mean, torch::Tensor rstd,
     torch::Tensor scale, torch::Tensor shift) {
-  dla::stem_check(x, "bn_relu_maxpool_bwd");
-  const int N = (int)x.size(0), C = (int)x.size(1);
-  const int H = (int)x.size(2), W = (int)x.size(3);
+  const char* fn = "bn_relu_maxpool_bwd";
+  const auto geo = dla::stem_geom(x, fn);
+  const int N = geo.N, C = geo.C, H = geo.H, W = geo.W;
   const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
-  const int64_t rows = (int64_t)N * H * W;
+  const int64_t rows = geo.rows;
   DLA_CHECK_CUDA(dpool);
   if (!dla::is_nhwc_rows(dpool))
     dpool = dpool.contiguous(at::MemoryFormat::ChannelsLast);
   const std::vector<int64_t> pshape{N, C, OH, OW};
   TORCH_CHECK(dpool.scalar_type() == x.scalar_type() &&
                   dpool.sizes() == at::IntArrayRef(pshape),
-              "bn_relu_maxpool_bwd: dpool must be [N, C, OH, OW] of x's dtype");
+              fn, ": dpool must be [N, C, OH, OW] of x's dtype");
   TORCH_CHECK(slots.is_cuda() && slots.scalar_type() == torch::kByte &&
                   slots.sizes() == at::IntArrayRef(pshape) &&
                   dla::is_nhwc_rows(slots),
-              "bn_relu_maxpool_bwd: slots must be channels_last uint8 "
-              "[N, C, OH, OW]");
-  for (const auto* t : {&mean, &rstd, &scale, &shift})
-    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kFloat &&
-                    t->is_contiguous() && t->numel() == C,
-                "bn_relu_maxpool_bwd: per-channel tensors must be contiguous "
-                "fp32 [C]");
-  TORCH_CHECK(weight.numel() == C, "bn_relu_maxpool_bwd: weight must be [C]");
+              fn, ": slots must be channels_last uint8 [N, C, OH, OW]");
+  dla::bn_check_channels({&mean, &rstd, &scale, &shift}, C, fn, true);
+  dla::bn_check_channels({&weight}, C, fn);
   torch::Tensor sums;
   auto dx = torch::empty_like(x);
   auto w32 = weight.to(torch::kFloat).contiguous();
   DLA_DISPATCH_FLOAT_TYPES(x.scalar_type(), "bn_relu_maxpool_bwd", [&] {
-    constexpr int V = 16 / (int)sizeof(dev_t);
-    const int lanes = C / V;
-    const auto t = dla::nhwc_red_tile(lanes, rows, dla::kStemRedBlocks,
+    constexpr int V = dla::kVecMax<dev_t>;
+    const auto t = dla::nhwc_red_tile(C / V, rows, dla::kStemRedBlocks,
                                       dla::kStemRedBlocks);
     auto slab = torch::empty({t.parts, 2 * C},
                              x.options().dtype(torch::kFloat));
@@ -1715,18 +1689,16 @@ std::vector<torch::Tensor> bn_relu_maxpool_bwd(
                        slab.data_ptr<float>(), C, H, W, OH, OW, rows, t.bl,
                        t.rb);
     sums = dla::bn_slab_reduce_launch(slab);
-    const int64_t used = dla::nhwc_used_threads(lanes, rows, 524288);
+    const auto grid = dla::nhwc_grid(C / V, rows);
     hipLaunchKernelGGL((dla::bn_relu_maxpool_bwd_dx_nhwc_kernel<dev_t, V>),
-                       dim3((int)((used + 255) / 256)), dim3(256), 0,
-                       dla::stream(), (const dev_t*)dpool.data_ptr(),
-                       slots.data_ptr<uint8_t>(), (const dev_t*)x.data_ptr(),
-                       scale.data_ptr<float>(), shift.data_ptr<float>(),
-                       mean.data_ptr<float>(), rstd.data_ptr<float>(),
-                       w32.data_ptr<float>(), sums.data_ptr<float>(),
-                       (dev_t*)dx.data_ptr(), C, H, W, OH, OW, rows, used,
-                       1.f / (float)rows);
+                       dim3(grid.blocks), dim3(256), 0, dla::stream(),
+                       (const dev_t*)dpool.data_ptr(), slots.data_ptr<uint8_t>(),
+                       (const dev_t*)x.data_ptr(), scale.data_ptr<float>(),
+                       shift.data_ptr<float>(), mean.data_ptr<float>(),
+                       rstd.data_ptr<float>(), w32.data_ptr<float>(),
+                       sums.data_ptr<float>(), (dev_t*)dx.data_ptr(), C, H, W,
+                       OH, OW, rows, grid.used, 1.f / (float)rows);
   });
   HIP_CHECK_ERR();
-  return {dx, dla::bn_param_grad(sums, C, C, weight),
-          dla::bn_param_grad(sums, 0, C, weight)};
+  return dla::bn_grads(dx, sums, C, weight);
 }

@@ -43,6 +43,19 @@ inline int grid_1d(int64_t n, int block) {
 
 inline hipStream_t stream() { return at::hip::getCurrentHIPStream().stream(); }
 
+// Threads of an elementwise kernel over a row-major [rows, lanes_per_row]
+// matrix of vector lanes (the NHWC BatchNorm apply/dx kernels, the stride-2
+// gather/scatter): whole rows only, about target_lanes of them, so that flat
+// thread t owns lane t % lanes_per_row of rows t / lanes_per_row, + used /
+// lanes_per_row, ...
+inline int64_t nhwc_used_threads(int lanes_per_row, int64_t rows,
+                                 int64_t target_lanes) {
+  int64_t k = target_lanes / lanes_per_row;
+  if (k > rows) k = rows;
+  if (k < 1) k = 1;
+  return (int64_t)lanes_per_row * k;
+}
+
 // ---- dtype conversion helpers ------------------------------------------------
 template <typename T> struct AccT { using type = float; };
 

@@ -12,15 +12,6 @@ namespace dla {
 
 using bf16 = __hip_bfloat16;
 
-// same thread-mapping helper as the NHWC batchnorm kernels
-inline int64_t nhwc_used_threads_pub(int lanes_per_row, int64_t rows,
-                                     int64_t target_lanes) {
-  int64_t k = target_lanes / lanes_per_row;
-  if (k > rows) k = rows;
-  if (k < 1) k = 1;
-  return (int64_t)lanes_per_row * k;
-}
-
 // 32x32 bf16 tiles through LDS, +1-element pad kills write bank conflicts.
 __global__ __launch_bounds__(256) void transpose2d_kernel(
     const bf16* __restrict__ src, bf16* __restrict__ dst, int R, int C) {
@@ -131,7 +122,7 @@ torch::Tensor stride2_gather(torch::Tensor x) {
     auto run = [&](auto vtag) {
       constexpr int VV = decltype(vtag)::value;
       const int lanes = C / VV;
-      const int64_t used = dla::nhwc_used_threads_pub(lanes, M_out, 262144);
+      const int64_t used = dla::nhwc_used_threads(lanes, M_out, 262144);
       hipLaunchKernelGGL((dla::stride2_gather_kernel<dev_t, VV>),
                          dim3((unsigned)((used + 255) / 256)),
                          dim3(256), 0, dla::stream(),
@@ -162,7 +153,7 @@ torch::Tensor stride2_scatter(torch::Tensor dy, int64_t IH, int64_t IW) {
     auto run = [&](auto vtag) {
       constexpr int VV = decltype(vtag)::value;
       const int lanes = C / VV;
-      const int64_t used = dla::nhwc_used_threads_pub(lanes, M_in, 524288);
+      const int64_t used = dla::nhwc_used_threads(lanes, M_in, 524288);
       hipLaunchKernelGGL((dla::stride2_scatter_kernel<dev_t, VV>),
                          dim3((unsigned)((used + 255) / 256)), dim3(256), 0,
                          dla::stream(), (const dev_t*)dy.data_ptr(),

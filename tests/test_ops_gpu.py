@@ -128,6 +128,105 @@ def test_batchnorm_train_channels_last(dtype, relu):
                                rtol=2e-2 if dtype != torch.float32 else 1e-4)
 
 
+def _bn_train_case(shape, dtype, relu, channels_last):
+    """Train forward and backward of ops.BatchNorm2d against an fp32
+    nn.BatchNorm2d on the same values, with test_batchnorm_train's bounds."""
+    torch.manual_seed(0)
+    N, C, H, W = shape
+    bn = ops.BatchNorm2d(C, relu=relu).to(DEV).to(dtype)
+    with torch.no_grad():
+        bn.weight.uniform_(0.5, 1.5)
+        bn.bias.uniform_(-0.5, 0.5)
+    bn_ref = torch.nn.BatchNorm2d(C).to(DEV).float()
+    bn_ref.load_state_dict({k: v.float() for k, v in bn.state_dict().items()})
+    fmt = torch.channels_last if channels_last else torch.contiguous_format
+    x = torch.randn(N, C, H, W, device=DEV, dtype=dtype).contiguous(
+        memory_format=fmt).requires_grad_(True)
+    y = bn(x)
+    assert y.is_contiguous(memory_format=fmt)
+    xr = x.detach().float().contiguous().requires_grad_(True)
+    yr = bn_ref(xr)
+    if relu:
+        yr = torch.relu(yr)
+    torch.testing.assert_close(y.float().contiguous(), yr, **_tol(dtype))
+    g = torch.randn_like(yr).to(dtype)  # same (rounded) grad to both paths
+    y.backward(g.contiguous(memory_format=fmt))
+    yr.backward(g.float())
+    assert x.grad.is_contiguous(memory_format=fmt)
+    torch.testing.assert_close(x.grad.float().contiguous(), xr.grad,
+                               atol=2e-2 if dtype != torch.float32 else 1e-4,
+                               rtol=2e-2 if dtype != torch.float32 else 1e-4)
+    rows = N * H * W
+    torch.testing.assert_close(bn.weight.grad.float(), bn_ref.weight.grad,
+                               atol=max(5e-2, 2e-3 * rows ** 0.5), rtol=2e-2)
+    torch.testing.assert_close(bn.running_mean.float(), bn_ref.running_mean,
+                               atol=1e-2, rtol=1e-2)
+    torch.testing.assert_close(bn.running_var.float(), bn_ref.running_var,
+                               atol=1e-2, rtol=1e-2)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("relu", [False, True])
+def test_batchnorm_train_nchw_scalar_apply(dtype, relu):
+    """NCHW with H*W = 9, no multiple of the vector width: the scalar
+    bn_apply_kernel<.., 1, R>. With relu this is the mask-from-y backward."""
+    _bn_train_case((2, 5, 3, 3), dtype, relu, channels_last=False)
+
+
+@pytest.mark.parametrize("relu", [False, True])
+def test_batchnorm_train_channels_last_c6(relu):
+    """NHWC with C = 6: the statistics kernels take V = 2, apply and dx V = 1."""
+    _bn_train_case((2, 6, 5, 5), torch.bfloat16, relu, channels_last=True)
+
+
+def _eval_bn_reference(x, bn, relu):
+    yr = F.batch_norm(x.float().contiguous(), bn.running_mean.float(),
+                      bn.running_var.float(), bn.weight.float(),
+                      bn.bias.float(), False, 0.0, bn.eps)
+    return torch.relu(yr) if relu else yr
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("relu", [False, True])
+@pytest.mark.parametrize("shape,channels_last", [
+    ((4, 32, 8, 8), True),   # NHWC, full-width vectors
+    ((2, 5, 3, 3), True),    # NHWC, V = 1
+    ((2, 5, 3, 3), False),   # NCHW, scalar apply
+])
+def test_batchnorm_eval_apply(dtype, relu, shape, channels_last):
+    torch.manual_seed(0)
+    C = shape[1]
+    bn = ops.BatchNorm2d(C, relu=relu).to(DEV).to(dtype).eval()
+    fmt = torch.channels_last if channels_last else torch.contiguous_format
+    with torch.no_grad():
+        bn.weight.uniform_(0.5, 1.5)
+        bn.bias.uniform_(-0.5, 0.5)
+        bn.running_mean.uniform_(-1, 1)
+        bn.running_var.uniform_(0.5, 2)
+        x = torch.randn(shape, device=DEV, dtype=dtype).contiguous(memory_format=fmt)
+        y = bn(x)
+        yr = _eval_bn_reference(x, bn, relu)
+    assert y.is_contiguous(memory_format=fmt)
+    torch.testing.assert_close(y.float().contiguous(), yr, **_tol(dtype))
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_frozen_batchnorm_channels_last(dtype):
+    torch.manual_seed(0)
+    bn = ops.FrozenBatchNorm2d(16).to(DEV).to(dtype)
+    with torch.no_grad():
+        bn.weight.uniform_(0.5, 1.5)
+        bn.bias.uniform_(-0.5, 0.5)
+        bn.running_mean.uniform_(-1, 1)
+        bn.running_var.uniform_(0.5, 2)
+        x = torch.randn(2, 16, 4, 4, device=DEV, dtype=dtype).contiguous(
+            memory_format=torch.channels_last)
+        y = bn(x)
+        yr = _eval_bn_reference(x, bn, False)
+    assert y.is_contiguous(memory_format=torch.channels_last)
+    torch.testing.assert_close(y.float().contiguous(), yr, **_tol(dtype))
+
+
 def test_add_relu_channels_last():
     torch.manual_seed(0)
     a = torch.randn(4, 32, 8, 8, device=DEV, dtype=torch.bfloat16).contiguous(
